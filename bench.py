@@ -14,9 +14,17 @@ scaling — every rank serves its own independent 512-key stream against a
 replicated table; `value` is the aggregate DPFs/sec over all ranks, using
 the MAX step time across ranks.
 
+A plain run only sets up, warms up, times the steps and prints the JSON
+result line.  `--full` adds everything else the benchmark verifies (today:
+the two-server reconstruction check, also available alone as `--check`).
+`--dump-outputs DIR` writes the shares the last timed step returned to
+DIR/shares.npy (float64, exact for int32) so two builds can be compared
+output for output: table and keys are seeded, hence identical across runs
+with the same arguments.
+
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
        [--entries N] [--prf AES128|SALSA20|CHACHA20] [--batch B]
-       [--mode replicate|shard]
+       [--mode replicate|shard] [--dump-outputs DIR] [--full]
 """
 
 import argparse
@@ -24,6 +32,7 @@ import json
 import os
 import time
 
+import numpy as np
 import torch
 
 from gpudpf import DPF, ShardedDPF, _core
@@ -44,12 +53,28 @@ V100_BASELINE = {
     ("CHACHA20", 1048576): 4054.0,
 }
 
+# --dump-outputs cap (bytes over all files); larger outputs are sampled
+DUMP_MAX_BYTES = 64 << 20
+
 PRF_IDS = {
     "DUMMY": DPF.PRF_DUMMY,
     "SALSA20": DPF.PRF_SALSA20,
     "CHACHA20": DPF.PRF_CHACHA20,
     "AES128": DPF.PRF_AES128,
 }
+
+
+def dump_outputs(out_dir, name, out):
+    """Write `out` (the [batch, e] int32 shares of the last timed step) as
+    out_dir/<name>.npy in float64.  Outputs beyond DUMP_MAX_BYTES are
+    reduced to a fixed, seeded sample of their flattened elements."""
+    arr = out.detach().cpu().numpy().astype(np.float64)
+    limit = DUMP_MAX_BYTES // arr.itemsize
+    if arr.size > limit:
+        pick = np.random.default_rng(0).choice(arr.size, limit, replace=False)
+        arr = arr.reshape(-1)[np.sort(pick)]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, name + ".npy"), arr)
 
 
 def main():
@@ -76,7 +101,17 @@ def main():
     ap.add_argument("--no-graph", action="store_true",
                     help="plain per-step launches instead of the hipGraph "
                          "serving loop")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="after timing, write the shares returned by the "
+                         "last timed step to DIR/shares.npy (float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline figure "
+                         "(the --check reconstruction check)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.full:
+        args.check = True
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -156,8 +191,10 @@ def main():
                     if len(pending) >= 2:
                         return srv.collect(pending.pop(0))
                 def drain():
+                    out = None
                     while pending:
-                        srv.collect(pending.pop(0))
+                        out = srv.collect(pending.pop(0))
+                    return out
         else:
             def step(k=keys_cpu):
                 return engine.eval_cpu(k)
@@ -178,15 +215,31 @@ def main():
         torch.distributed.barrier()
         sync()
 
+    # `last` is what the newest completed step returned (the pipelined
+    # loop hands back batch i-1 at step i and the tail in drain()).
+    last = None
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
-    drain()
+        out = step()
+        if out is not None:
+            last = out
+    out = drain()
+    if out is not None:
+        last = out
     sync()
     t1 = time.perf_counter()
     if distributed:
         torch.distributed.barrier()
         sync()
+
+    if args.dump_outputs:
+        # shard mode: every rank holds the same all-reduced shares
+        if args.mode == "shard" and distributed:
+            name = "shares" if rank == 0 else None
+        else:
+            name = "shares" if world == 1 else "shares_rank%d" % rank
+        if name:
+            dump_outputs(args.dump_outputs, name, last)
 
     if args.check:
         if on_gpu:
@@ -195,6 +248,11 @@ def main():
         else:
             ea = step(keys_cpu)
             eb = step(keys2_cpu)
+        # the timed serving loop must return what a plain evaluation does
+        if not torch.equal(last.cpu(), ea.cpu()):
+            raise SystemExit("bench --check FAILED: the timed path's shares "
+                             "differ from a plain evaluation (rank %d, "
+                             "mode %s)" % (rank, args.mode))
         rec = (ea.to(torch.int64) - eb.to(torch.int64)).to(torch.int32)
         want = table[alphas, : args.entry_size]
         if not torch.equal(rec.cpu(), want):

@@ -1,6 +1,7 @@
 // Host-side API of the gpudpf HIP kernel library (implemented in
 // dpf_kernels.hip, bound to python in hip_bindings.cc).
 #pragma once
+#include <cstddef>
 #include <cstdint>
 
 namespace gpudpf_hip {
@@ -10,15 +11,22 @@ namespace gpudpf_hip {
 //   table: device ptr, u32 [n][16]          (leaf_perm-reordered rows)
 //   out:   device ptr, u32 [batch][16]
 //   aes_tabs: device ptr to 5*256 u32 AES tables (only read for AES128)
+//   scratch:  0 = the shared per-device sibling-stack scratch (launches on
+//             one stream at a time); launches that may overlap on different
+//             streams each pass their own device buffer of at least
+//             eval_scratch_bytes(batch, depth, zlog) bytes (launch_expand too)
 void launch_fused(std::uintptr_t keys, std::uintptr_t table, std::uintptr_t out,
                   std::uintptr_t aes_tabs, int batch, long long n, int depth,
-                  int zlog, int prf, std::uintptr_t stream);
+                  int zlog, int prf, std::uintptr_t stream,
+                  std::uintptr_t scratch = 0, std::size_t scratch_bytes = 0);
+std::size_t eval_scratch_bytes(int batch, int depth, int zlog);
 
 // Full expansion to low-32 one-hot shares, permuted row order
 //   out: device ptr, u32 [batch][n]  (row r = leaf_perm(idx))
 void launch_expand(std::uintptr_t keys, std::uintptr_t out,
                    std::uintptr_t aes_tabs, int batch, long long n, int depth,
-                   int zlog, int prf, std::uintptr_t stream);
+                   int zlog, int prf, std::uintptr_t stream,
+                   std::uintptr_t scratch = 0, std::size_t scratch_bytes = 0);
 
 // Level-synchronized breadth-first expansion (the reference's
 // dpf_breadth_first.cu strategy): depth kernel launches, ping-pong u128

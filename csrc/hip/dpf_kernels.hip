@@ -1322,8 +1322,10 @@ size_t fused_shmem_bytes(int Z, int DS, int prf) {
 // Grow-only per-device scratch for the global stack levels.  Reused
 // across launches; sized for the largest request seen.  NOTE: concurrent
 // fused/expand launches on DIFFERENT streams of one device would share
-// this buffer — the python API serializes launches per DPF call, which
-// is the supported pattern.
+// this buffer (workgroups with equal blockIdx of two kernels in flight
+// overwrite each other's sibling stacks) — the python API serializes
+// launches per DPF call; servers that overlap launches across streams
+// pass a scratch buffer of their own per stream (eval_scratch_bytes).
 //
 // Outgrown buffers are RETIRED, never freed: a hipGraph captured while a
 // launch used the old buffer holds its raw pointer and replays against it
@@ -1350,19 +1352,36 @@ uint4* get_scratch(size_t bytes, hipStream_t /*stream*/) {
   return reinterpret_cast<uint4*>(g_scratch[dev]);
 }
 
-template <int PRF, bool FUSED>
-void launch_eval_t(const int* keys, const u32* table, u32* out,
-                   const u32* aes_tabs, int batch, long long n, int depth,
-                   int zlog, hipStream_t stream) {
-  const int Z = 1 << zlog;
-  const int DS = depth - zlog;
-  // j-split: grow the grid to >= 1024 workgroups (4 per CU) so small
-  // batches still fill the chip; each extra split costs one targeted
-  // descent (DS-1 pair expansions) per workgroup — negligible against
-  // pairs/2^slog leaf pairs.
+// j-split: grow the grid to >= 1024 workgroups (4 per CU) so small
+// batches still fill the chip; each extra split costs one targeted
+// descent (DS-1 pair expansions) per workgroup — negligible against
+// pairs/2^slog leaf pairs.
+int eval_slog(int batch, int DS) {
   int slog = 0;
   while ((batch << (slog + 1)) <= 2048 && slog + 2 <= DS - 1 && slog < 8)
     ++slog;
+  return slog;
+}
+
+// Bytes of global sibling-stack scratch one fused/expand launch touches:
+// one Z-wide uint4 row per workgroup and global stack level.
+size_t eval_scratch_need(int batch, int depth, int zlog) {
+  const int Z = 1 << zlog;
+  const int DS = depth - zlog;
+  int lds_levels = DS > 3 ? DS - 3 : 0;
+  if (lds_levels > MAX_LDS_LEVELS) lds_levels = MAX_LDS_LEVELS;
+  const int glob_levels = (DS > 3 ? DS - 3 : 0) - lds_levels;
+  return (size_t)(batch << eval_slog(batch, DS)) * glob_levels * Z * 16;
+}
+
+template <int PRF, bool FUSED>
+void launch_eval_t(const int* keys, const u32* table, u32* out,
+                   const u32* aes_tabs, int batch, long long n, int depth,
+                   int zlog, hipStream_t stream, uint4* own_scratch,
+                   size_t own_scratch_bytes) {
+  const int Z = 1 << zlog;
+  const int DS = depth - zlog;
+  const int slog = eval_slog(batch, DS);
   const size_t shmem = fused_shmem_bytes(Z, DS, PRF);
   auto kern = dpf_eval_kernel<PRF, FUSED>;
   if (shmem > 65536) {
@@ -1370,11 +1389,18 @@ void launch_eval_t(const int* keys, const u32* table, u32* out,
                                   hipFuncAttributeMaxDynamicSharedMemorySize,
                                   (int)shmem));
   }
-  int lds_levels = DS > 3 ? DS - 3 : 0;
-  if (lds_levels > MAX_LDS_LEVELS) lds_levels = MAX_LDS_LEVELS;
-  const int glob_levels = (DS > 3 ? DS - 3 : 0) - lds_levels;
-  uint4* scratch = get_scratch(
-      (size_t)(batch << slog) * glob_levels * Z * 16, stream);
+  // Caller-owned scratch (launches that may overlap on different streams
+  // each bring their own) or the shared per-device buffer.
+  const size_t need = eval_scratch_need(batch, depth, zlog);
+  uint4* scratch;
+  if (own_scratch) {
+    if (own_scratch_bytes < need)
+      throw std::invalid_argument("scratch buffer smaller than "
+                                  "eval_scratch_bytes(batch, depth, zlog)");
+    scratch = own_scratch;
+  } else {
+    scratch = get_scratch(need, stream);
+  }
   hipLaunchKernelGGL(kern, dim3((unsigned)(batch << slog)), dim3((unsigned)Z),
                      shmem, stream, keys, table, out, aes_tabs, scratch,
                      depth, zlog, slog, n);
@@ -1385,7 +1411,8 @@ template <bool FUSED>
 void launch_eval_dispatch(std::uintptr_t keys, std::uintptr_t table,
                           std::uintptr_t out, std::uintptr_t aes_tabs,
                           int batch, long long n, int depth, int zlog, int prf,
-                          std::uintptr_t stream) {
+                          std::uintptr_t stream, std::uintptr_t scratch,
+                          std::size_t scratch_bytes) {
   if (batch <= 0) return;
   if (depth < 1 || ((long long)1 << depth) != n)
     throw std::invalid_argument("bad depth/n");
@@ -1396,11 +1423,12 @@ void launch_eval_dispatch(std::uintptr_t keys, std::uintptr_t table,
   auto* o = reinterpret_cast<u32*>(out);
   auto* a = reinterpret_cast<const u32*>(aes_tabs);
   auto s = reinterpret_cast<hipStream_t>(stream);
+  auto* sc = reinterpret_cast<uint4*>(scratch);
   switch (prf) {
-    case PRF_DUMMY: launch_eval_t<PRF_DUMMY, FUSED>(k, tb, o, a, batch, n, depth, zlog, s); break;
-    case PRF_SALSA20: launch_eval_t<PRF_SALSA20, FUSED>(k, tb, o, a, batch, n, depth, zlog, s); break;
-    case PRF_CHACHA20: launch_eval_t<PRF_CHACHA20, FUSED>(k, tb, o, a, batch, n, depth, zlog, s); break;
-    case PRF_AES128: launch_eval_t<PRF_AES128, FUSED>(k, tb, o, a, batch, n, depth, zlog, s); break;
+    case PRF_DUMMY: launch_eval_t<PRF_DUMMY, FUSED>(k, tb, o, a, batch, n, depth, zlog, s, sc, scratch_bytes); break;
+    case PRF_SALSA20: launch_eval_t<PRF_SALSA20, FUSED>(k, tb, o, a, batch, n, depth, zlog, s, sc, scratch_bytes); break;
+    case PRF_CHACHA20: launch_eval_t<PRF_CHACHA20, FUSED>(k, tb, o, a, batch, n, depth, zlog, s, sc, scratch_bytes); break;
+    case PRF_AES128: launch_eval_t<PRF_AES128, FUSED>(k, tb, o, a, batch, n, depth, zlog, s, sc, scratch_bytes); break;
     default: throw std::invalid_argument("unknown PRF");
   }
 }
@@ -1409,16 +1437,24 @@ void launch_eval_dispatch(std::uintptr_t keys, std::uintptr_t table,
 
 void launch_fused(std::uintptr_t keys, std::uintptr_t table, std::uintptr_t out,
                   std::uintptr_t aes_tabs, int batch, long long n, int depth,
-                  int zlog, int prf, std::uintptr_t stream) {
+                  int zlog, int prf, std::uintptr_t stream,
+                  std::uintptr_t scratch, std::size_t scratch_bytes) {
   launch_eval_dispatch<true>(keys, table, out, aes_tabs, batch, n, depth, zlog,
-                             prf, stream);
+                             prf, stream, scratch, scratch_bytes);
+}
+
+std::size_t eval_scratch_bytes(int batch, int depth, int zlog) {
+  if (batch <= 0 || zlog < 6 || zlog >= depth)
+    throw std::invalid_argument("bad batch/depth/zlog");
+  return eval_scratch_need(batch, depth, zlog);
 }
 
 void launch_expand(std::uintptr_t keys, std::uintptr_t out,
                    std::uintptr_t aes_tabs, int batch, long long n, int depth,
-                   int zlog, int prf, std::uintptr_t stream) {
+                   int zlog, int prf, std::uintptr_t stream,
+                   std::uintptr_t scratch, std::size_t scratch_bytes) {
   launch_eval_dispatch<false>(keys, /*table=*/0, out, aes_tabs, batch, n, depth,
-                              zlog, prf, stream);
+                              zlog, prf, stream, scratch, scratch_bytes);
 }
 
 void launch_naive(std::uintptr_t keys, std::uintptr_t out,

@@ -61,11 +61,15 @@ PYBIND11_MODULE(_hip, m) {
   m.def("eval_fused", &gpudpf_hip::launch_fused, py::arg("keys"),
         py::arg("table"), py::arg("out"), py::arg("aes_tabs"), py::arg("batch"),
         py::arg("n"), py::arg("depth"), py::arg("zlog"), py::arg("prf"),
-        py::arg("stream"),
+        py::arg("stream"), py::arg("scratch") = 0,
+        py::arg("scratch_bytes") = 0,
         py::call_guard<py::gil_scoped_release>());
+  m.def("eval_scratch_bytes", &gpudpf_hip::eval_scratch_bytes,
+        py::arg("batch"), py::arg("depth"), py::arg("zlog"));
   m.def("eval_expand", &gpudpf_hip::launch_expand, py::arg("keys"),
         py::arg("out"), py::arg("aes_tabs"), py::arg("batch"), py::arg("n"),
         py::arg("depth"), py::arg("zlog"), py::arg("prf"), py::arg("stream"),
+        py::arg("scratch") = 0, py::arg("scratch_bytes") = 0,
         py::call_guard<py::gil_scoped_release>());
   m.def("eval_bfs", &gpudpf_hip::launch_bfs, py::arg("keys"), py::arg("out"),
         py::arg("aes_tabs"), py::arg("batch"), py::arg("n"), py::arg("depth"),

@@ -164,10 +164,18 @@ class PipelinedServer:
         dev = dpf._table_gpu.device
         self.device = dev
         n = dpf._n_domain
+        # Adjacent batches' kernels are in flight together on the slots'
+        # streams, so each slot owns its sibling-stack scratch: on the
+        # shared per-device buffer equal-numbered workgroups of the two
+        # kernels overwrite each other's stacks (n >= 2^16) and the shares
+        # come out wrong.
+        scratch_bytes = _hip.eval_scratch_bytes(batch, dpf._depth, dpf._zlog)
         self._slots = []
         for _ in range(depth):
             slot = {
                 "stream": torch.cuda.Stream(dev),
+                "scratch": torch.empty(scratch_bytes, dtype=torch.uint8,
+                                       device=dev),
                 "keys_pinned": torch.zeros((batch, DPF.KEY_INTS),
                                            dtype=torch.int32).pin_memory(),
                 "keys_gpu": torch.zeros((batch, DPF.KEY_INTS),
@@ -187,9 +195,10 @@ class PipelinedServer:
                                 dpf._table_gpu.data_ptr(),
                                 s["out_gpu"].data_ptr(), dpf._aes_ptr, batch,
                                 n, dpf._depth, dpf._zlog, dpf.prf_method,
-                                stream)
+                                stream, s["scratch"].data_ptr(),
+                                scratch_bytes)
 
-            warm = torch.cuda.Stream(dev)
+            warm =torch.cuda.Stream(dev)
             warm.wait_stream(torch.cuda.current_stream(dev))
             with torch.cuda.stream(warm):
                 for _ in range(3):
@@ -269,10 +278,16 @@ class TwoStageServer:
             raise Exception("pipeline share buffers need %d bytes "
                             "(free %d); lower batch/depth" % (need, free))
         self._gemm_stream = torch.cuda.Stream(dev)
+        # expansions of adjacent batches can overlap on the slots' streams:
+        # per-slot sibling-stack scratch (see PipelinedServer)
+        self._scratch_bytes = _hip.eval_scratch_bytes(batch, dpf._depth,
+                                                      dpf._zlog)
         self._slots = []
         for _ in range(depth):
             self._slots.append({
                 "stream": torch.cuda.Stream(dev),
+                "scratch": torch.empty(self._scratch_bytes,
+                                       dtype=torch.uint8, device=dev),
                 "keys_pinned": torch.zeros((batch, DPF.KEY_INTS),
                                            dtype=torch.int32).pin_memory(),
                 "keys_gpu": torch.zeros((batch, DPF.KEY_INTS),
@@ -306,7 +321,8 @@ class TwoStageServer:
             _hip.eval_expand(slot["keys_gpu"].data_ptr(),
                              slot["shares"].data_ptr(), dpf._aes_ptr,
                              self.batch, n, dpf._depth, dpf._zlog,
-                             dpf.prf_method, slot["stream"].cuda_stream)
+                             dpf.prf_method, slot["stream"].cuda_stream,
+                             slot["scratch"].data_ptr(), self._scratch_bytes)
             slot["ev_expand"].record(slot["stream"])
         # the GEMM stream serializes table passes across slots (the table
         # stream is the contended resource); it only waits for THIS

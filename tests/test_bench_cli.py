@@ -68,6 +68,38 @@ def test_bench_world2_gloo_check(mode):
         assert rec["config"]["global_batch"] == 16
 
 
+def test_bench_dump_outputs_and_full(tmp_path):
+    """--dump-outputs writes the last timed step's shares as float64, the
+    same values from run to run (seeded inputs) whatever --steps is, and
+    --full (which runs the reconstruction check) changes neither them nor
+    the result line's keys."""
+    import numpy as np
+
+    base = [sys.executable, "bench.py", "--device", "cpu",
+            "--entries", "8192", "--batch", "8", "--warmup", "1",
+            "--prf", "SALSA20"]
+    recs, dumps = [], []
+    for i, extra in enumerate((["--steps", "2"], ["--steps", "3", "--full"])):
+        out_dir = tmp_path / ("run%d" % i)
+        r = subprocess.run(base + extra + ["--dump-outputs", str(out_dir)],
+                           cwd=REPO, capture_output=True, text=True,
+                           timeout=300)
+        assert r.returncode == 0, r.stdout + r.stderr
+        recs.append(_last_json_line(r.stdout))
+        assert sorted(p.name for p in out_dir.iterdir()) == ["shares.npy"]
+        dumps.append(np.load(out_dir / "shares.npy"))
+    assert [rec["steps"] for rec in recs] == [2, 3]
+    for rec in recs:
+        assert rec["ms_per_step"] > 0
+        assert rec["value"] == pytest.approx(
+            8 / (rec["ms_per_step"] / 1000.0), rel=0.05)
+    assert recs[0].keys() == recs[1].keys()
+    assert dumps[0].dtype == np.float64 and dumps[0].shape == (8, 16)
+    assert np.array_equal(dumps[0], dumps[0].astype(np.int32))  # exact int32
+    assert np.any(dumps[0] != 0)
+    assert np.array_equal(dumps[0], dumps[1])
+
+
 def test_bench_single_process_cpu_wide_entries():
     # wide entry sizes must not crash the serving-mode selection
     cmd = [sys.executable, "bench.py", "--device", "cpu",

@@ -116,6 +116,40 @@ def test_gpu_pipelined_server_interleaved_batches():
         assert torch.equal(got, want)
 
 
+def test_gpu_pipelined_server_deep_tree_overlap():
+    # n >= 2^16 puts the shallow sibling-stack levels in global scratch.
+    # The two slots' kernels are in flight together (each submit is queued
+    # while the previous batch still runs), so every slot must use scratch
+    # of its own: every step's shares must equal the serial path's.
+    # The flagship shape: its ~18 ms kernels overlap almost entirely, and
+    # on one shared scratch buffer nearly every step came out wrong
+    # (smaller shapes overlap too briefly to show it).
+    from gpudpf.serving import PipelinedServer
+
+    n, batch = 1 << 20, 512
+    dpf = DPF(prf=DPF.PRF_AES128)
+    table = torch.randint(-(2**31), 2**31 - 1, (n, 16),
+                          dtype=torch.int64).to(torch.int32)
+    dpf.eval_init(table)
+    batches = [torch.stack([torch.from_numpy(_core.gen(
+        (r * 7919 + i * 131) % n, n, b"deep-%d-%d" % (r, i),
+        DPF.PRF_AES128)[0]) for i in range(batch)]) for r in range(2)]
+    want = [dpf.eval_gpu(ks) for ks in batches]
+    srv = PipelinedServer(dpf, batch, depth=2)
+    pending, results = [], []
+    for step in range(24):  # the collisions set in after ~15 steps
+        pending.append((srv.submit(batches[step % 2]), step % 2))
+        if len(pending) >= 2:
+            h, r = pending.pop(0)
+            results.append((srv.collect(h), r))
+    while pending:
+        h, r = pending.pop(0)
+        results.append((srv.collect(h), r))
+    assert len(results) == 24
+    for step, (got, r) in enumerate(results):
+        assert torch.equal(got, want[r]), step
+
+
 def test_gpu_two_stage_server_pipelined():
     # wide-entry pipelined serving: expansion of batch i+1 overlaps the
     # GEMM of batch i; results must match the plain two-stage path
