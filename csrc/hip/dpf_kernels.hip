@@ -1,9 +1,10 @@
 // MI355X (gfx950, CDNA4) HIP kernels for DPF expansion + fused PIR lookup.
 //
 // Design (MI355X-first, not a port — see SURVEY.md §7):
-//   * One key per workgroup of Z = 1<<zlog threads (Z = 256 = 4 wave64 for
-//     n >= 512).  Grid = batch, so a 512-key batch puts >=2 workgroups on
-//     each of the 256 CUs.
+//   * One UNIT of Z = 1<<zlog threads (Z = 256 = 4 wave64 for n >= 512)
+//     per (key, DFS segment); a 512-key batch is 2048 units.  A workgroup
+//     is one unit, except for AES, where up to four units form one
+//     workgroup and share the T-table (eval_units_per_wg).
 //   * Phase 1: breadth-first expansion of the GGM root to Z frontier seeds
 //     through an LDS ping-pong (zlog levels, ~2Z PRFs — negligible).
 //   * Phase 2: each thread owns ONE subtree and walks it with a sibling-
@@ -12,7 +13,7 @@
 //     accesses are conflict-free b128 ops.  The two HOT stack levels
 //     (popped on 3/4 of all steps) live in registers; the cold remainder
 //     shares the phase-1 ping-pong LDS region (they are never live at the
-//     same time), keeping LDS small enough for 3-4 workgroups per CU.
+//     same time), keeping LDS small enough for 3-4 units per CU.
 //   * Each visited interior node expands BOTH children from one parent;
 //     for AES this shares one key schedule across the two encryptions
 //     (the reference re-expands per call: dpf_gpu/prf/prf.cu:159-184,
@@ -24,12 +25,14 @@
 //     traffic than the reference's mod-2^128 MAC (dpf_hybrid.cu:166-172),
 //     with bit-identical output.  Table loads are issued BEFORE the leaf
 //     PRFs of the same step, so ~1000 cycles of cipher work hides them.
-//   * AES T-table: a single 256-entry table replicated 32-way and
-//     interleaved (entry*32 + lane%32) so every lane reads its own LDS
-//     bank — measured 4.3x bank-conflict amplification with flat tables
-//     (SQ_LDS_BANK_CONFLICT 3.5e10 vs SQ_INSTS_LDS 8.1e9, profiles/).
+//   * AES T-table: a single 256-entry table replicated 64-way (byte
+//     entry*256 + (lane%64)*4, at LDS byte 0) so every lane reads its own
+//     LDS bank — measured 4.3x bank-conflict amplification with flat
+//     tables (SQ_LDS_BANK_CONFLICT 3.5e10 vs SQ_INSTS_LDS 8.1e9,
+//     profiles/) — and a lookup address is one v_perm_b32 of a state word.
 //     te1..te3 are byte rotations of te0 (1 v_alignbit per lookup) and
-//     sbox[x] = byte2 of te0[x], so one table serves the whole cipher.
+//     sbox[x] = byte2 of te0[x], so one table serves the whole cipher;
+//     the five-term round sums are two 3-input xors (v_bitop3_b32).
 //   * Table layout: row(idx) = j<<(zlog+1) | t<<1 | b (leaf_perm in
 //     csrc/core/dpf_core.cc): at DFS step j the workgroup reads one
 //     contiguous 32 KB slab; every lane reads its two rows as 8 contiguous
@@ -41,7 +44,9 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cstdlib>
 #include <mutex>
+#include <set>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -61,6 +66,22 @@ using u64 = std::uint64_t;
                                hipGetErrorString(_e) + " at " __FILE__   \
                                ":" + std::to_string(__LINE__));          \
   } while (0)
+
+// Launches that ask for 64 KiB or more of dynamic LDS (every kernel that
+// holds the replicated AES table) must raise the kernel's limit first.
+// Done once per (kernel, device), so a launch replayed or captured later
+// makes no runtime call beyond the launch itself.
+inline void allow_large_lds(const void* kern) {
+  static std::mutex mu;
+  static std::set<std::pair<const void*, int>> done;
+  int dev = 0;
+  HIP_CHECK(hipGetDevice(&dev));
+  std::lock_guard<std::mutex> lock(mu);
+  if (done.count({kern, dev})) return;
+  HIP_CHECK(hipFuncSetAttribute(
+      kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  done.insert({kern, dev});
+}
 
 // ---------------------------------------------------------------------------
 // 128-bit helpers (uint4 limbs, x = bits 31..0 ... w = bits 127..96)
@@ -86,11 +107,13 @@ __device__ __forceinline__ u32 rotr24(u32 v) { return (v >> 24) | (v << 8); }
 #define PRF_AES128 3
 
 // AES replicated-table geometry
-#define AES_REP 32
+#define AES_REP 64
 // DFS sibling-stack levels kept in LDS (deeper levels: registers;
 // shallower: global scratch)
 #define MAX_LDS_LEVELS 4
-#define AES_LDS_WORDS (256 * AES_REP)  // 32 KiB
+#define AES_LDS_WORDS (256 * AES_REP)  // 64 KiB
+// Most (key, segment) units one AES workgroup walks (they share the table)
+#define AES_MAX_UNITS 4
 
 // ---------------------------------------------------------------------------
 // DUMMY: seed*(pos+4242) + (pos+4242) over Z_2^128
@@ -328,18 +351,68 @@ __device__ __forceinline__ void chacha12_pair_low_core(uint4 seed, u32& lo0,
 }
 
 // ---------------------------------------------------------------------------
-// AES-128, replicated-LDS variant (fused kernel).  aes_lds holds te0
-// replicated AES_REP-way, interleaved: word(entry e, copy c) at e*32+c.
-// Lane l always uses copy l%32 => bank (addr/4)%32 == l%32: conflict-free.
+// AES-128, replicated-LDS variant (fused kernel).  The LDS holds te0
+// replicated AES_REP = 64-way with a 256-byte entry stride: word (entry e,
+// copy c) sits at LDS byte e*256 + c*4, and lane l always uses copy l%64.
+//   * Bank = (addr/4)%32 = l%32 inside each 32-lane ds_read_b32 group:
+//     conflict-free.
+//   * The byte address of te0[byte K of w] is ONE v_perm_b32: byte 1 of
+//     the address is byte K of w, byte 0 is lane*4 (<= 252), bytes 2..3
+//     are zero.  (The 32-way layout needed bfe + shift-add + add.)
+//   * The table starts at LDS byte 0, so that integer IS the address: the
+//     access is formed as an address_space(3) load from it, with no add
+//     of a table base.  This relies on every kernel that builds an AesLds
+//     having no static LDS (dynamic LDS then starts at 0) and placing the
+//     table first in its dynamic LDS map.
 //   te0[x] bytes (MSB..LSB) = [2s, s, s, 3s];  te1 = ror8(te0),
 //   te2 = ror16, te3 = ror24;  sbox[x] = byte2 of te0[x].
 // ---------------------------------------------------------------------------
 struct AesLds {
-  const u32* rep;  // replicated te0
-  u32 lane;        // threadIdx.x % 32
-  __device__ __forceinline__ u32 te0(u32 x) const { return rep[x * AES_REP + lane]; }
-  __device__ __forceinline__ u32 sbox(u32 x) const { return (te0(x) >> 16) & 0xff; }
+  u32 lane4;  // (threadIdx.x % 64) * 4
+  typedef __attribute__((address_space(3))) const u32 lds_u32;
+  static __device__ __forceinline__ u32 ld(u32 byte_addr) {
+    return *reinterpret_cast<lds_u32*>(byte_addr);
+  }
+  // byte address of te0[byte K of w] (K = 0 is the LSB)
+  template <int K>
+  __device__ __forceinline__ u32 addr_b(u32 w) const {
+    return __builtin_amdgcn_perm(w, lane4, 0x0c0c0000u | ((4u + K) << 8));
+  }
+  template <int K>
+  __device__ __forceinline__ u32 te0_b(u32 w) const { return ld(addr_b<K>(w)); }
+  template <int K>
+  __device__ __forceinline__ u32 sbox_b(u32 w) const {
+    return (te0_b<K>(w) >> 16) & 0xff;
+  }
+  __device__ __forceinline__ u32 te0(u32 x) const { return ld((x << 8) | lane4); }
 };
+
+// Stage the replicated te0 table at LDS byte 0 (all threads of the
+// workgroup; the caller synchronizes).  `lds0` must be the start of the
+// kernel's dynamic LDS.  Word index e*64 + c => consecutive threads write
+// consecutive banks.
+__device__ __forceinline__ void aes_stage_table(u32* lds0,
+                                                const u32* __restrict__ aes_tabs) {
+  for (int idx = (int)threadIdx.x; idx < AES_LDS_WORDS; idx += (int)blockDim.x)
+    lds0[idx] = aes_tabs[idx >> 6];  // global layout: te0 at offset 0
+}
+
+__device__ __forceinline__ u32 xor3(u32 a, u32 b, u32 c) {
+  return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96);  // a ^ b ^ c
+}
+
+// [S(a) S(b) S(c) S(d)] (MSB..LSB) from the four te0 words of a..d: sbox
+// is byte 2 of te0, gathered by two v_perm_b32 with disjoint bytes (the
+// caller xors the halves into its sum).
+#define AES_SB_HI(ta, tb) __builtin_amdgcn_perm(ta, tb, 0x06020c0cu)
+#define AES_SB_LO(tc, td) __builtin_amdgcn_perm(tc, td, 0x0c0c0602u)
+
+// One MixColumns output word: te0[a.b3] ^ te1[b.b2] ^ te2[c.b1] ^
+// te3[d.b0] ^ k as two 3-input xors.
+#define AES_COL(T, a, b, c, d, k)                                         \
+  xor3(xor3((T).template te0_b<3>(a), rotr8((T).template te0_b<2>(b)),    \
+            rotr16((T).template te0_b<1>(c))),                            \
+       rotr24((T).template te0_b<0>(d)), k)
 
 // Both children (pos 0 and pos 1) with an ON-THE-FLY key schedule fused
 // into the interleaved cipher rounds: the key-expansion sbox chain (4
@@ -367,109 +440,93 @@ __device__ __forceinline__ void aes_cipher_pair(uint4 seed, const AesLds& T,
   // compile with -DGPUDPF_AES_NOSHARE for the straight dual-cipher
   // variant (measured comparison in profiles/PROFILING.md).
   {
-    // round 1
-    u32 w_ = (k3 << 8) | (k3 >> 24);
-    w_ = (T.sbox((w_ >> 24) & 0xff) << 24) | (T.sbox((w_ >> 16) & 0xff) << 16) |
-         (T.sbox((w_ >> 8) & 0xff) << 8) | T.sbox(w_ & 0xff);
-    w_ ^= (rcon << 24);
+    // round 1.  s3 == k3 here (the position byte only enters s0), so the
+    // four te0 words of s3 the cipher round reads anyway also carry the
+    // sbox bytes of the round-1 key schedule: no separate sbox lookups.
+    const u32 t33 = T.te0_b<3>(s3), t32 = T.te0_b<2>(s3),
+              t31 = T.te0_b<1>(s3), t30 = T.te0_b<0>(s3);
+    k0 = xor3(AES_SB_HI(t32, t31), AES_SB_LO(t30, t33), k0) ^ (rcon << 24);
     rcon = 0x02u;
-    k0 ^= w_; k1 ^= k0; k2 ^= k1; k3 ^= k2;
-    const u32 A = T.te0(s0 >> 24);
-    u32 n0 = A ^ rotr8(T.te0((s1 >> 16) & 0xff)) ^
-             rotr16(T.te0((s2 >> 8) & 0xff)) ^ rotr24(T.te0(s3 & 0xff)) ^ k0;
-    u32 n1 = T.te0(s1 >> 24) ^ rotr8(T.te0((s2 >> 16) & 0xff)) ^
-             rotr16(T.te0((s3 >> 8) & 0xff)) ^ rotr24(T.te0(s0 & 0xff)) ^ k1;
-    u32 n2 = T.te0(s2 >> 24) ^ rotr8(T.te0((s3 >> 16) & 0xff)) ^
-             rotr16(T.te0((s0 >> 8) & 0xff)) ^ rotr24(T.te0(s1 & 0xff)) ^ k2;
-    u32 n3 = T.te0(s3 >> 24) ^ rotr8(T.te0((s0 >> 16) & 0xff)) ^
-             rotr16(T.te0((s1 >> 8) & 0xff)) ^ rotr24(T.te0(s2 & 0xff)) ^ k3;
-    const u32 m0 = n0 ^ A ^ T.te0((s0 >> 24) ^ 1u);
+    k1 ^= k0; k2 ^= k1; k3 ^= k2;
+    const u32 a0 = T.addr_b<3>(s0);
+    const u32 A = AesLds::ld(a0);
+    u32 n0 = xor3(xor3(A, rotr8(T.te0_b<2>(s1)), rotr16(T.te0_b<1>(s2))),
+                  rotr24(t30), k0);
+    u32 n1 = xor3(xor3(T.te0_b<3>(s1), rotr8(T.te0_b<2>(s2)), rotr16(t31)),
+                  rotr24(T.te0_b<0>(s0)), k1);
+    u32 n2 = xor3(xor3(T.te0_b<3>(s2), rotr8(t32), rotr16(T.te0_b<1>(s0))),
+                  rotr24(T.te0_b<0>(s1)), k2);
+    u32 n3 = xor3(xor3(t33, rotr8(T.te0_b<2>(s0)), rotr16(T.te0_b<1>(s1))),
+                  rotr24(T.te0_b<0>(s2)), k3);
+    // child b differs in bit 0 of byte (s0 >> 24): entry index ^ 1 is
+    // address ^ 256
+    const u32 m0 = xor3(n0, A, AesLds::ld(a0 ^ 256u));
     // round 2
-    w_ = (k3 << 8) | (k3 >> 24);
-    w_ = (T.sbox((w_ >> 24) & 0xff) << 24) | (T.sbox((w_ >> 16) & 0xff) << 16) |
-         (T.sbox((w_ >> 8) & 0xff) << 8) | T.sbox(w_ & 0xff);
-    w_ ^= (rcon << 24);
+    k0 = xor3(AES_SB_HI(T.te0_b<2>(k3), T.te0_b<1>(k3)),
+              AES_SB_LO(T.te0_b<0>(k3), T.te0_b<3>(k3)), k0) ^ (rcon << 24);
     rcon = 0x04u;
-    k0 ^= w_; k1 ^= k0; k2 ^= k1; k3 ^= k2;
-    const u32 c0 = rotr8(T.te0((n1 >> 16) & 0xff)) ^
-                   rotr16(T.te0((n2 >> 8) & 0xff)) ^
-                   rotr24(T.te0(n3 & 0xff)) ^ k0;
-    const u32 c1 = T.te0(n1 >> 24) ^ rotr8(T.te0((n2 >> 16) & 0xff)) ^
-                   rotr16(T.te0((n3 >> 8) & 0xff)) ^ k1;
-    const u32 c2 = T.te0(n2 >> 24) ^ rotr8(T.te0((n3 >> 16) & 0xff)) ^
-                   rotr24(T.te0(n1 & 0xff)) ^ k2;
-    const u32 c3 = T.te0(n3 >> 24) ^ rotr16(T.te0((n1 >> 8) & 0xff)) ^
-                   rotr24(T.te0(n2 & 0xff)) ^ k3;
-    s0 = T.te0(n0 >> 24) ^ c0;
-    u0 = T.te0(m0 >> 24) ^ c0;
-    s1 = rotr24(T.te0(n0 & 0xff)) ^ c1;
-    u1 = rotr24(T.te0(m0 & 0xff)) ^ c1;
-    s2 = rotr16(T.te0((n0 >> 8) & 0xff)) ^ c2;
-    u2 = rotr16(T.te0((m0 >> 8) & 0xff)) ^ c2;
-    s3 = rotr8(T.te0((n0 >> 16) & 0xff)) ^ c3;
-    u3 = rotr8(T.te0((m0 >> 16) & 0xff)) ^ c3;
+    k1 ^= k0; k2 ^= k1; k3 ^= k2;
+    const u32 c0 = xor3(rotr8(T.te0_b<2>(n1)), rotr16(T.te0_b<1>(n2)),
+                        rotr24(T.te0_b<0>(n3))) ^ k0;
+    const u32 c1 = xor3(T.te0_b<3>(n1), rotr8(T.te0_b<2>(n2)),
+                        rotr16(T.te0_b<1>(n3))) ^ k1;
+    const u32 c2 = xor3(T.te0_b<3>(n2), rotr8(T.te0_b<2>(n3)),
+                        rotr24(T.te0_b<0>(n1))) ^ k2;
+    const u32 c3 = xor3(T.te0_b<3>(n3), rotr16(T.te0_b<1>(n1)),
+                        rotr24(T.te0_b<0>(n2))) ^ k3;
+    s0 = T.te0_b<3>(n0) ^ c0;
+    u0 = T.te0_b<3>(m0) ^ c0;
+    s1 = rotr24(T.te0_b<0>(n0)) ^ c1;
+    u1 = rotr24(T.te0_b<0>(m0)) ^ c1;
+    s2 = rotr16(T.te0_b<1>(n0)) ^ c2;
+    u2 = rotr16(T.te0_b<1>(m0)) ^ c2;
+    s3 = rotr8(T.te0_b<2>(n0)) ^ c3;
+    u3 = rotr8(T.te0_b<2>(m0)) ^ c3;
     r_begin = 3;
   }
 #endif
 #pragma unroll
   for (int r = r_begin; r < 10; ++r) {
     // next round key (k0..k3 become rk[4r..4r+3])
-    u32 w_ = (k3 << 8) | (k3 >> 24);
-    w_ = (T.sbox((w_ >> 24) & 0xff) << 24) | (T.sbox((w_ >> 16) & 0xff) << 16) |
-         (T.sbox((w_ >> 8) & 0xff) << 8) | T.sbox(w_ & 0xff);
-    w_ ^= (rcon << 24);
+    k0 = xor3(AES_SB_HI(T.te0_b<2>(k3), T.te0_b<1>(k3)),
+              AES_SB_LO(T.te0_b<0>(k3), T.te0_b<3>(k3)), k0) ^ (rcon << 24);
     rcon = (rcon << 1) ^ ((rcon & 0x80u) ? 0x11bu : 0u);
     rcon &= 0xffu;
-    k0 ^= w_; k1 ^= k0; k2 ^= k1; k3 ^= k2;
+    k1 ^= k0; k2 ^= k1; k3 ^= k2;
     // cipher round r for both children
-    u32 n0 = T.te0(s0 >> 24) ^ rotr8(T.te0((s1 >> 16) & 0xff)) ^
-             rotr16(T.te0((s2 >> 8) & 0xff)) ^ rotr24(T.te0(s3 & 0xff)) ^ k0;
-    u32 m0 = T.te0(u0 >> 24) ^ rotr8(T.te0((u1 >> 16) & 0xff)) ^
-             rotr16(T.te0((u2 >> 8) & 0xff)) ^ rotr24(T.te0(u3 & 0xff)) ^ k0;
-    u32 n1 = T.te0(s1 >> 24) ^ rotr8(T.te0((s2 >> 16) & 0xff)) ^
-             rotr16(T.te0((s3 >> 8) & 0xff)) ^ rotr24(T.te0(s0 & 0xff)) ^ k1;
-    u32 m1 = T.te0(u1 >> 24) ^ rotr8(T.te0((u2 >> 16) & 0xff)) ^
-             rotr16(T.te0((u3 >> 8) & 0xff)) ^ rotr24(T.te0(u0 & 0xff)) ^ k1;
-    u32 n2 = T.te0(s2 >> 24) ^ rotr8(T.te0((s3 >> 16) & 0xff)) ^
-             rotr16(T.te0((s0 >> 8) & 0xff)) ^ rotr24(T.te0(s1 & 0xff)) ^ k2;
-    u32 m2 = T.te0(u2 >> 24) ^ rotr8(T.te0((u3 >> 16) & 0xff)) ^
-             rotr16(T.te0((u0 >> 8) & 0xff)) ^ rotr24(T.te0(u1 & 0xff)) ^ k2;
-    u32 n3 = T.te0(s3 >> 24) ^ rotr8(T.te0((s0 >> 16) & 0xff)) ^
-             rotr16(T.te0((s1 >> 8) & 0xff)) ^ rotr24(T.te0(s2 & 0xff)) ^ k3;
-    u32 m3 = T.te0(u3 >> 24) ^ rotr8(T.te0((u0 >> 16) & 0xff)) ^
-             rotr16(T.te0((u1 >> 8) & 0xff)) ^ rotr24(T.te0(u2 & 0xff)) ^ k3;
+    u32 n0 = AES_COL(T, s0, s1, s2, s3, k0);
+    u32 m0 = AES_COL(T, u0, u1, u2, u3, k0);
+    u32 n1 = AES_COL(T, s1, s2, s3, s0, k1);
+    u32 m1 = AES_COL(T, u1, u2, u3, u0, k1);
+    u32 n2 = AES_COL(T, s2, s3, s0, s1, k2);
+    u32 m2 = AES_COL(T, u2, u3, u0, u1, k2);
+    u32 n3 = AES_COL(T, s3, s0, s1, s2, k3);
+    u32 m3 = AES_COL(T, u3, u0, u1, u2, k3);
     s0 = n0; s1 = n1; s2 = n2; s3 = n3;
     u0 = m0; u1 = m1; u2 = m2; u3 = m3;
   }
   // round-10 key
-  {
-    u32 w_ = (k3 << 8) | (k3 >> 24);
-    w_ = (T.sbox((w_ >> 24) & 0xff) << 24) | (T.sbox((w_ >> 16) & 0xff) << 16) |
-         (T.sbox((w_ >> 8) & 0xff) << 8) | T.sbox(w_ & 0xff);
-    w_ ^= (rcon << 24);
-    k0 ^= w_; k1 ^= k0; k2 ^= k1; k3 ^= k2;
-  }
-  u32 o0 = ((T.sbox(s0 >> 24) << 24) | (T.sbox((s1 >> 16) & 0xff) << 16) |
-            (T.sbox((s2 >> 8) & 0xff) << 8) | T.sbox(s3 & 0xff)) ^ k0;
-  u32 p0 = ((T.sbox(u0 >> 24) << 24) | (T.sbox((u1 >> 16) & 0xff) << 16) |
-            (T.sbox((u2 >> 8) & 0xff) << 8) | T.sbox(u3 & 0xff)) ^ k0;
+  k0 = xor3(AES_SB_HI(T.te0_b<2>(k3), T.te0_b<1>(k3)),
+            AES_SB_LO(T.te0_b<0>(k3), T.te0_b<3>(k3)), k0) ^ (rcon << 24);
+  k1 ^= k0; k2 ^= k1; k3 ^= k2;
+  // last round: [S(a.b3) S(b.b2) S(c.b1) S(d.b0)] ^ k
+#define AES_LAST(a, b, c, d, k)                               \
+  xor3(AES_SB_HI(T.te0_b<3>(a), T.te0_b<2>(b)),               \
+       AES_SB_LO(T.te0_b<1>(c), T.te0_b<0>(d)), k)
+  u32 o0 = AES_LAST(s0, s1, s2, s3, k0);
+  u32 p0 = AES_LAST(u0, u1, u2, u3, k0);
   if constexpr (LOW) {
     ra = make_uint4(__builtin_bswap32(o0), 0, 0, 0);
     rb = make_uint4(__builtin_bswap32(p0), 0, 0, 0);
     return;
   }
-  u32 o1 = ((T.sbox(s1 >> 24) << 24) | (T.sbox((s2 >> 16) & 0xff) << 16) |
-            (T.sbox((s3 >> 8) & 0xff) << 8) | T.sbox(s0 & 0xff)) ^ k1;
-  u32 p1 = ((T.sbox(u1 >> 24) << 24) | (T.sbox((u2 >> 16) & 0xff) << 16) |
-            (T.sbox((u3 >> 8) & 0xff) << 8) | T.sbox(u0 & 0xff)) ^ k1;
-  u32 o2 = ((T.sbox(s2 >> 24) << 24) | (T.sbox((s3 >> 16) & 0xff) << 16) |
-            (T.sbox((s0 >> 8) & 0xff) << 8) | T.sbox(s1 & 0xff)) ^ k2;
-  u32 p2 = ((T.sbox(u2 >> 24) << 24) | (T.sbox((u3 >> 16) & 0xff) << 16) |
-            (T.sbox((u0 >> 8) & 0xff) << 8) | T.sbox(u1 & 0xff)) ^ k2;
-  u32 o3 = ((T.sbox(s3 >> 24) << 24) | (T.sbox((s0 >> 16) & 0xff) << 16) |
-            (T.sbox((s1 >> 8) & 0xff) << 8) | T.sbox(s2 & 0xff)) ^ k3;
-  u32 p3 = ((T.sbox(u3 >> 24) << 24) | (T.sbox((u0 >> 16) & 0xff) << 16) |
-            (T.sbox((u1 >> 8) & 0xff) << 8) | T.sbox(u2 & 0xff)) ^ k3;
+  u32 o1 = AES_LAST(s1, s2, s3, s0, k1);
+  u32 p1 = AES_LAST(u1, u2, u3, u0, k1);
+  u32 o2 = AES_LAST(s2, s3, s0, s1, k2);
+  u32 p2 = AES_LAST(u2, u3, u0, u1, k2);
+  u32 o3 = AES_LAST(s3, s0, s1, s2, k3);
+  u32 p3 = AES_LAST(u3, u0, u1, u2, k3);
+#undef AES_LAST
   ra = make_uint4(__builtin_bswap32(o0), __builtin_bswap32(o1),
                   __builtin_bswap32(o2), __builtin_bswap32(o3));
   rb = make_uint4(__builtin_bswap32(p0), __builtin_bswap32(p1),
@@ -544,26 +601,40 @@ __device__ __forceinline__ void expand_pair(uint4 seed, int i,
 }
 
 // ---------------------------------------------------------------------------
-// Main kernel.  LDS map (u32 granularity):
-//   [cw: 128 uint4][shared: Z*max(2, DS-3) uint4][aes: 0/8192 u32][red]
+// Main kernel.  A UNIT is Z threads walking one (key, segment) pair; a
+// workgroup holds K units (K = 1 except for AES, where the K units share
+// one 64 KiB te0 table so the table does not cost occupancy).  Dynamic LDS
+// map (the kernel has no static LDS, so it starts at LDS byte 0):
+//   [aes: 0/16384 u32] then K unit slices of
+//   [cw: 128 uint4][shared: Z*max(2, min(DS-3, 4)) uint4][red: Z/64*16 u32]
 // The `shared` region is the phase-1 ping-pong (2*Z uint4) first, then the
-// cold DFS stack (levels 1..DS-3) — never live simultaneously.
+// cold DFS stack (LDS levels) — never live simultaneously.
 // Hot stack levels DS-1 / DS-2 are the registers rtop1 / rtop2.
+//
+// Multi-unit indexing: unit = blockIdx.x*K + threadIdx.x/Z, t = threadIdx.x
+// % Z.  Z is a multiple of 64, so a wave never straddles units and every
+// per-unit branch is wave-uniform.  Units never communicate: key, segment,
+// scratch row, cw/stack/red slices all index by unit, and partial sums
+// meet only in the wrapping atomics.  The workgroup barriers (staging,
+// the zlog phase-1 levels, the reduction) have trip counts that depend on
+// kernel arguments only; surplus units of the last workgroup (unit >=
+// n_units) join them but load no key or table data, write no scratch and
+// issue no atomics.
 // ---------------------------------------------------------------------------
 // slog: log2 of the DFS range split — each key's 2^(DS-1) leaf pairs are
-// divided over 2^slog workgroups (j-split).  The split changes neither the
-// table layout nor the per-thread subtree assignment: workgroup (key, seg)
+// divided over 2^slog units (j-split).  The split changes neither the
+// table layout nor the per-thread subtree assignment: unit (key, seg)
 // walks pairs [seg*P, (seg+1)*P) of every thread's subtree, paying one
 // extra targeted descent (DS-1 pair expansions) to enter at seg*P.  Fused
 // partials combine with wrapping u32 atomicAdd (exact mod 2^32).  This is
-// what fills 256 CUs at small batch (batch 512 alone = only 2 WGs/CU) and
+// what fills 256 CUs at small batch (batch 512 alone = only 2 units/CU) and
 // doubles as the single-key low-latency mode (the reference needs a
 // separate cooperative-groups kernel for that: dpf_coop.cu).
-template <int PRF, bool FUSED>
-__global__ __launch_bounds__(256) void dpf_eval_kernel(
+template <int PRF, bool FUSED, int K>
+__global__ __launch_bounds__(256 * K) void dpf_eval_kernel(
     const int* __restrict__ keys, const u32* __restrict__ table,
     u32* __restrict__ out, const u32* __restrict__ aes_tabs,
-    uint4* __restrict__ scratch, int depth, int zlog, int slog,
+    uint4* __restrict__ scratch, int depth, int zlog, int slog, int n_units,
     long long n) {
   extern __shared__ u32 smem[];
   const int Z = 1 << zlog;
@@ -571,37 +642,38 @@ __global__ __launch_bounds__(256) void dpf_eval_kernel(
   // Sibling-stack placement by pop frequency (level d pops once per
   // 2^(DS-1-d) pairs): deepest two levels in registers, the next
   // MAX_LDS_LEVELS in LDS, the shallow remainder in global scratch
-  // (touched <= 1/64 of steps) — keeping LDS small enough for 3+
-  // workgroups per CU even with the 32 KB AES table resident.
+  // (touched <= 1/64 of steps) — keeping the per-unit LDS slice small
+  // enough that four units fit beside the 64 KB AES table.
   const int lds_levels =
       DS > 3 ? (DS - 3 < MAX_LDS_LEVELS ? DS - 3 : MAX_LDS_LEVELS) : 0;
   const int lds_base = DS - 2 - lds_levels;  // levels [lds_base, DS-3] in LDS
   const int glob_levels = (DS - 3) - lds_levels;  // levels [1, lds_base-1]
-  const int t = (int)threadIdx.x;
-  const int key_id = (int)(blockIdx.x >> slog);
-  const int seg = (int)(blockIdx.x & ((1u << slog) - 1));
+  const int t = (int)threadIdx.x & (Z - 1);
+  const int u_local = K == 1 ? 0 : (int)threadIdx.x >> zlog;
+  const int unit = (int)blockIdx.x * K + u_local;
+  const bool active = unit < n_units;  // wave-uniform (Z % 64 == 0)
+  const int key_id = unit >> slog;
+  const int seg = unit & ((1 << slog) - 1);
   const long long key_base = (long long)key_id * 524;
 
-  uint4* cw_lds = reinterpret_cast<uint4*>(smem);   // 128 entries
-  uint4* shared_region = cw_lds + 128;
   const int shared_u4 = Z * (lds_levels > 2 ? lds_levels : 2);
-  uint4* gstack = scratch + (size_t)blockIdx.x * (glob_levels > 0 ? glob_levels : 0) * Z;
-  u32* aes_lds = reinterpret_cast<u32*>(shared_region + shared_u4);
-  u32* red = aes_lds + (PRF == PRF_AES128 ? AES_LDS_WORDS : 0);
+  const int unit_u32 = (128 + shared_u4) * 4 + (Z >> 6) * 16;
+  u32* unit_lds =
+      smem + (PRF == PRF_AES128 ? AES_LDS_WORDS : 0) + u_local * unit_u32;
+  uint4* cw_lds = reinterpret_cast<uint4*>(unit_lds);   // 128 entries
+  uint4* shared_region = cw_lds + 128;
+  u32* red = reinterpret_cast<u32*>(shared_region + shared_u4);
+  uint4* gstack = scratch + (size_t)unit * (glob_levels > 0 ? glob_levels : 0) * Z;
 
-  // Stage codewords; replicate the AES te0 table 32-way interleaved.
-  for (int idx = t; idx < 128; idx += blockDim.x)
-    cw_lds[idx] = reinterpret_cast<const uint4*>(keys + key_base + 4)[idx];
-  if constexpr (PRF == PRF_AES128) {
-    for (int e = t; e < 256; e += blockDim.x) {
-      const u32 v = aes_tabs[e];  // global layout: te0 at offset 0
-#pragma unroll
-      for (int c = 0; c < AES_REP; ++c) aes_lds[e * AES_REP + c] = v;
-    }
+  // Stage codewords per unit; the AES te0 table once per workgroup.
+  if (active) {
+    for (int idx = t; idx < 128; idx += Z)
+      cw_lds[idx] = reinterpret_cast<const uint4*>(keys + key_base + 4)[idx];
   }
-  AesLds T{aes_lds, (u32)(t & (AES_REP - 1))};
+  if constexpr (PRF == PRF_AES128) aes_stage_table(smem, aes_tabs);
+  AesLds T{((u32)threadIdx.x & 63u) << 2};
   uint4* pp = shared_region;
-  if (t == 0) {
+  if (active && t == 0) {
     const int* rp = keys + key_base + 516;
     pp[0] = make_uint4((u32)rp[0], (u32)rp[1], (u32)rp[2], (u32)rp[3]);
   }
@@ -613,7 +685,7 @@ __global__ __launch_bounds__(256) void dpf_eval_kernel(
   uint4* b = pp + Z;
   for (int l = 1; l <= zlog; ++l) {
     const int i = depth - l;
-    if (t < (1 << l)) {
+    if (active && t < (1 << l)) {
       uint4 parent = a[t >> 1];
       uint4 v = prf_full<PRF>(parent, (u32)(t & 1), T);
       const int sel = (int)(parent.x & 1u);
@@ -628,92 +700,100 @@ __global__ __launch_bounds__(256) void dpf_eval_kernel(
   __syncthreads();  // everyone holds their frontier seed; pp is now free
   uint4* stack = shared_region;  // LDS stack levels [lds_base, DS-3]
 
-  // Targeted descent to leaf-pair j_lo: at split d take bit (DS-1-d) of
-  // j_lo, always recording the bit-1 child in the level's sibling slot
-  // (when the bit is 1 the slot is stale, but it is provably rewritten by
-  // a later descent before its next pop).
-  const long long pairs = 1LL << (DS - 1);
-  const long long j_lo = (long long)seg * (pairs >> slog);
-  const long long j_hi = j_lo + (pairs >> slog);
-  uint4 rtop1 = cur, rtop2 = cur;  // hot levels DS-1 / DS-2
-  for (int d = 1; d <= DS - 1; ++d) {
-    uint4 c0, c1;
-    expand_pair<PRF>(cur, DS - d, cw_lds, T, c0, c1);
-    if (d == DS - 1) rtop1 = c1;
-    else if (d == DS - 2) rtop2 = c1;
-    else if (d >= lds_base) stack[(d - lds_base) * Z + t] = c1;
-    else gstack[(size_t)(d - 1) * Z + t] = c1;
-    cur = ((j_lo >> (DS - 1 - d)) & 1) ? c1 : c0;
-  }
-
   u32 acc[16];
 #pragma unroll
   for (int w = 0; w < 16; ++w) acc[w] = 0;
 
-  // leaf-level correction words (eval level 0) are read every iteration:
-  // hoist their low words into registers
-  const u32 cwl[2][2] = {{cw_lds[0].x, cw_lds[1].x},
-                         {cw_lds[64].x, cw_lds[65].x}};
-
-  for (long long j = j_lo; j < j_hi; ++j) {
-    // Issue the two table-row loads first: the leaf ciphers below hide
-    // their latency.
-    uint4 r0q[4], r1q[4];
-    if constexpr (FUSED) {
-      const uint4* rows =
-          reinterpret_cast<const uint4*>(table + ((j << (zlog + 1)) +
-                                                  ((long long)t << 1)) * 16);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        r0q[q] = rows[q];
-        r1q[q] = rows[q + 4];
-      }
-    }
-
-    u32 v0, v1;
-    {
-      u32 p0, p1;
-      prf_pair_low<PRF>(cur, T, p0, p1);
-      const int sel = (int)(cur.x & 1u);
-      v0 = p0 + cwl[sel][0];
-      v1 = p1 + cwl[sel][1];
-    }
-
-    if constexpr (FUSED) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        acc[4 * q + 0] += v0 * r0q[q].x + v1 * r1q[q].x;
-        acc[4 * q + 1] += v0 * r0q[q].y + v1 * r1q[q].y;
-        acc[4 * q + 2] += v0 * r0q[q].z + v1 * r1q[q].z;
-        acc[4 * q + 3] += v0 * r0q[q].w + v1 * r1q[q].w;
-      }
-    } else {
-      u32* orow = out + (u64)key_id * (u64)n +
-                  (u64)((j << (zlog + 1)) + ((long long)t << 1));
-      orow[0] = v0;
-      orow[1] = v1;
-    }
-
-    if (j + 1 == j_hi) break;
-    // Pop the deepest pending sibling (register-resident on 3/4 of steps)
-    // and descend its bit-0 spine.
-    const int c = (int)(__ffsll((unsigned long long)(j + 1)) - 1);
-    if (c == 0) {
-      cur = rtop1;
-      continue;  // next leaf-parent is the sibling itself
-    }
-    const int dpop = DS - 1 - c;
-    cur = (c == 1) ? rtop2
-          : (dpop >= lds_base) ? stack[(dpop - lds_base) * Z + t]
-                               : gstack[(size_t)(dpop - 1) * Z + t];
-    for (int d = dpop + 1; d <= DS - 1; ++d) {
+  if (active) {
+    // Targeted descent to leaf-pair j_lo: at split d take bit (DS-1-d) of
+    // j_lo, always recording the bit-1 child in the level's sibling slot
+    // (when the bit is 1 the slot is stale, but it is provably rewritten by
+    // a later descent before its next pop).
+    const long long pairs = 1LL << (DS - 1);
+    const long long j_lo = (long long)seg * (pairs >> slog);
+    const long long j_hi = j_lo + (pairs >> slog);
+    uint4 rtop1 = cur, rtop2 = cur;  // hot levels DS-1 / DS-2
+    for (int d = 1; d <= DS - 1; ++d) {
       uint4 c0, c1;
       expand_pair<PRF>(cur, DS - d, cw_lds, T, c0, c1);
       if (d == DS - 1) rtop1 = c1;
       else if (d == DS - 2) rtop2 = c1;
       else if (d >= lds_base) stack[(d - lds_base) * Z + t] = c1;
       else gstack[(size_t)(d - 1) * Z + t] = c1;
-      cur = c0;
+      cur = ((j_lo >> (DS - 1 - d)) & 1) ? c1 : c0;
+    }
+
+    // leaf-level correction words (eval level 0) are read every iteration:
+    // hoist their low words into registers.  For AES, whose K = 4 kernel
+    // has 128 VGPRs to live in, into scalar ones: the values are the same
+    // for the whole unit, hence for the wave.
+    auto uni = [](u32 v) -> u32 {
+      if constexpr (PRF == PRF_AES128) return __builtin_amdgcn_readfirstlane(v);
+      else return v;
+    };
+    const u32 cwl[2][2] = {{uni(cw_lds[0].x), uni(cw_lds[1].x)},
+                           {uni(cw_lds[64].x), uni(cw_lds[65].x)}};
+
+    for (long long j = j_lo; j < j_hi; ++j) {
+      // Issue the two table-row loads first: the leaf ciphers below hide
+      // their latency.
+      uint4 r0q[4], r1q[4];
+      if constexpr (FUSED) {
+        const uint4* rows =
+            reinterpret_cast<const uint4*>(table + ((j << (zlog + 1)) +
+                                                    ((long long)t << 1)) * 16);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          r0q[q] = rows[q];
+          r1q[q] = rows[q + 4];
+        }
+      }
+
+      u32 v0, v1;
+      {
+        u32 p0, p1;
+        prf_pair_low<PRF>(cur, T, p0, p1);
+        const int sel = (int)(cur.x & 1u);
+        v0 = p0 + cwl[sel][0];
+        v1 = p1 + cwl[sel][1];
+      }
+
+      if constexpr (FUSED) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          acc[4 * q + 0] += v0 * r0q[q].x + v1 * r1q[q].x;
+          acc[4 * q + 1] += v0 * r0q[q].y + v1 * r1q[q].y;
+          acc[4 * q + 2] += v0 * r0q[q].z + v1 * r1q[q].z;
+          acc[4 * q + 3] += v0 * r0q[q].w + v1 * r1q[q].w;
+        }
+      } else {
+        u32* orow = out + (u64)key_id * (u64)n +
+                    (u64)((j << (zlog + 1)) + ((long long)t << 1));
+        orow[0] = v0;
+        orow[1] = v1;
+      }
+
+      if (j + 1 == j_hi) break;
+      // Pop the deepest pending sibling (register-resident on 3/4 of steps)
+      // and descend its bit-0 spine.
+      const int c = (int)(__ffsll((unsigned long long)(j + 1)) - 1);
+      if (c == 0) {
+        cur = rtop1;
+        continue;  // next leaf-parent is the sibling itself
+      }
+      const int dpop = DS - 1 - c;
+      cur = (c == 1) ? rtop2
+            : (dpop >= lds_base) ? stack[(dpop - lds_base) * Z + t]
+                                 : gstack[(size_t)(dpop - 1) * Z + t];
+      for (int d = dpop + 1; d <= DS - 1; ++d) {
+        uint4 c0, c1;
+        expand_pair<PRF>(cur, DS - d, cw_lds, T, c0, c1);
+        if (d == DS - 1) rtop1 = c1;
+        else if (d == DS - 2) rtop2 = c1;
+        else if (d >= lds_base) stack[(d - lds_base) * Z + t] = c1;
+        else gstack[(size_t)(d - 1) * Z + t] = c1;
+        cur = c0;
+      }
     }
   }
 
@@ -726,13 +806,14 @@ __global__ __launch_bounds__(256) void dpf_eval_kernel(
       for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
       acc[w] = v;
     }
-    const int lane = t & 63, wave = t >> 6, nwaves = (int)blockDim.x >> 6;
+    // (per unit: wave = the unit's own wave index, red = its own slice)
+    const int lane = t & 63, wave = t >> 6, nwaves = Z >> 6;
     if (lane == 0) {
 #pragma unroll
       for (int w = 0; w < 16; ++w) red[wave * 16 + w] = acc[w];
     }
     __syncthreads();
-    if (t < 16) {
+    if (active && t < 16) {
       u32 s = 0;
       for (int wv = 0; wv < nwaves; ++wv) s += red[wv * 16 + t];
       // Wrapping u32 atomic add combines the 2^slog segment partials
@@ -847,19 +928,14 @@ __global__ __launch_bounds__(256) void dpf_naive_kernel(
 // kernel's pair rate divided by this is its efficiency.
 // ---------------------------------------------------------------------------
 template <int PRF>
-__global__ __launch_bounds__(256) void prf_sol_kernel(
+__global__ __launch_bounds__(PRF == PRF_AES128 ? 1024 : 256) void prf_sol_kernel(
     const u32* __restrict__ aes_tabs, u32* __restrict__ out, int iters) {
   extern __shared__ u32 smem[];
-  u32* aes_lds = smem;
   if constexpr (PRF == PRF_AES128) {
-    for (int e = (int)threadIdx.x; e < 256; e += blockDim.x) {
-      const u32 v = aes_tabs[e];
-#pragma unroll
-      for (int c = 0; c < AES_REP; ++c) aes_lds[e * AES_REP + c] = v;
-    }
+    aes_stage_table(smem, aes_tabs);  // table first: LDS byte 0
     __syncthreads();
   }
-  AesLds T{aes_lds, (u32)(threadIdx.x & 31)};
+  AesLds T{((u32)threadIdx.x & 63u) << 2};
   uint4 seed = make_uint4(threadIdx.x + 1, blockIdx.x + 2, 3, 4);
   for (int i = 0; i < iters; ++i) {
     uint4 r0, r1;
@@ -886,7 +962,13 @@ void launch_prf_sol(std::uintptr_t aes_tabs, std::uintptr_t out, int blocks,
       hipLaunchKernelGGL(prf_sol_kernel<PRF_CHACHA20>, dim3(blocks), dim3(256), shmem, st, a, o, iters);
       break;
     case PRF_AES128:
-      hipLaunchKernelGGL(prf_sol_kernel<PRF_AES128>, dim3(blocks), dim3(256), shmem, st, a, o, iters);
+      allow_large_lds((const void*)prf_sol_kernel<PRF_AES128>);
+      // Same thread count in workgroups of 1024 where it divides: like the
+      // eval kernel's K = 4, four times the waves share one 64 KiB table.
+      if (blocks % 4 == 0)
+        hipLaunchKernelGGL(prf_sol_kernel<PRF_AES128>, dim3(blocks / 4), dim3(1024), shmem, st, a, o, iters);
+      else
+        hipLaunchKernelGGL(prf_sol_kernel<PRF_AES128>, dim3(blocks), dim3(256), shmem, st, a, o, iters);
       break;
     default:
       throw std::invalid_argument("unknown PRF");
@@ -914,19 +996,12 @@ __global__ __launch_bounds__(256) void dpf_bfs_level_kernel(
     uint4* __restrict__ children, u32* __restrict__ out,
     const u32* __restrict__ aes_tabs, int level, int depth, long long n) {
   extern __shared__ u32 smem[];
-  u32* aes_lds = smem;
   uint4* cw_lvl = reinterpret_cast<uint4*>(
-      smem + (PRF == PRF_AES128 ? AES_LDS_WORDS : 0));
+      smem + (PRF == PRF_AES128 ? AES_LDS_WORDS : 0));  // table first
   const int t = (int)threadIdx.x;
   const int key_id = (int)blockIdx.y;
   const long long key_base = (long long)key_id * 524;
-  if constexpr (PRF == PRF_AES128) {
-    for (int e = t; e < 256; e += blockDim.x) {
-      const u32 v = aes_tabs[e];
-#pragma unroll
-      for (int c = 0; c < AES_REP; ++c) aes_lds[e * AES_REP + c] = v;
-    }
-  }
+  if constexpr (PRF == PRF_AES128) aes_stage_table(smem, aes_tabs);
   // stage this level's 4 correction words (cw[sel][2i+b], i = eval level)
   const int i_eval = depth - 1 - level;
   if (t < 4) {
@@ -935,7 +1010,7 @@ __global__ __launch_bounds__(256) void dpf_bfs_level_kernel(
         [sel * 64 + i_eval * 2 + b];
   }
   __syncthreads();
-  AesLds T{aes_lds, (u32)(t & (AES_REP - 1))};
+  AesLds T{((u32)t & 63u) << 2};
 
   const long long n_parents = (long long)1 << level;
   const long long p = (long long)blockIdx.x * blockDim.x + t;
@@ -989,17 +1064,12 @@ __global__ __launch_bounds__(256) void dpf_coop_kernel(
     uint4* __restrict__ ping, uint4* __restrict__ pong, int depth, int zlog,
     long long n) {
   extern __shared__ u32 smem[];
-  u32* aes_lds = smem;
   const int t = (int)threadIdx.x;
   if constexpr (PRF == PRF_AES128) {
-    for (int e = t; e < 256; e += blockDim.x) {
-      const u32 v = aes_tabs[e];
-#pragma unroll
-      for (int c = 0; c < AES_REP; ++c) aes_lds[e * AES_REP + c] = v;
-    }
+    aes_stage_table(smem, aes_tabs);  // table first: LDS byte 0
     __syncthreads();
   }
-  AesLds T{aes_lds, (u32)(t & (AES_REP - 1))};
+  AesLds T{((u32)t & 63u) << 2};
   auto grid = cooperative_groups::this_grid();
   const long long gsize = (long long)gridDim.x * blockDim.x;
   const long long gtid = (long long)blockIdx.x * blockDim.x + t;
@@ -1102,16 +1172,11 @@ __global__ __launch_bounds__(256) void probe_prf_kernel(
     uint4* __restrict__ single0, uint4* __restrict__ single1,
     u32* __restrict__ low0, u32* __restrict__ low1, int count) {
   extern __shared__ u32 smem[];
-  u32* aes_lds = smem;
   if constexpr (PRF == PRF_AES128) {
-    for (int e = (int)threadIdx.x; e < 256; e += blockDim.x) {
-      const u32 v = aes_tabs[e];
-#pragma unroll
-      for (int c = 0; c < AES_REP; ++c) aes_lds[e * AES_REP + c] = v;
-    }
+    aes_stage_table(smem, aes_tabs);  // table first: LDS byte 0
     __syncthreads();
   }
-  AesLds T{aes_lds, (u32)(threadIdx.x & (AES_REP - 1))};
+  AesLds T{((u32)threadIdx.x & 63u) << 2};
   const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
   if (i >= count) return;
   const uint4 s = seeds[i];
@@ -1172,6 +1237,7 @@ void launch_probe_prf(std::uintptr_t seeds, std::uintptr_t aes_tabs,
                          count);
       break;
     case PRF_AES128:
+      allow_large_lds((const void*)probe_prf_kernel<PRF_AES128>);
       hipLaunchKernelGGL(probe_prf_kernel<PRF_AES128>, dim3(blocks), dim3(256),
                          shmem, st, sp, ap, p0, p1, s0, s1, l0, l1, count);
       break;
@@ -1190,6 +1256,7 @@ void launch_coop_t(const int* keys, const u32* table, u32* out,
                    int zlog, long long n, hipStream_t st) {
   auto kern = dpf_coop_kernel<PRF, FUSED>;
   const size_t shmem = (PRF == PRF_AES128) ? AES_LDS_WORDS * 4 : 0;
+  if (PRF == PRF_AES128) allow_large_lds((const void*)kern);
   int dev = 0;
   HIP_CHECK(hipGetDevice(&dev));
   int coop = 0;
@@ -1256,6 +1323,8 @@ void launch_bfs_t(const int* keys, u32* out, const u32* aes_tabs,
                   hipStream_t st) {
   const size_t shmem =
       (PRF == PRF_AES128 ? AES_LDS_WORDS * 4 : 0) + 4 * sizeof(uint4);
+  if (PRF == PRF_AES128)
+    allow_large_lds((const void*)dpf_bfs_level_kernel<PRF>);
   for (int level = 0; level < depth; ++level) {
     const long long n_parents = (long long)1 << level;
     const long long blocks = (n_parents + 255) / 256;
@@ -1309,20 +1378,20 @@ void launch_bfs(std::uintptr_t keys, std::uintptr_t out,
 // ---------------------------------------------------------------------------
 namespace {
 
-size_t fused_shmem_bytes(int Z, int DS, int prf) {
+// Dynamic LDS of one eval workgroup of K units (the kernel's LDS map).
+size_t fused_shmem_bytes(int Z, int DS, int prf, int K) {
   int lds_levels = DS > 3 ? DS - 3 : 0;
   if (lds_levels > MAX_LDS_LEVELS) lds_levels = MAX_LDS_LEVELS;
-  size_t bytes = 128 * 16;                                  // codewords
-  bytes += (size_t)Z * (lds_levels > 2 ? lds_levels : 2) * 16;  // pp/stack
-  if (prf == PRF_AES128) bytes += AES_LDS_WORDS * 4;        // replicated te0
-  bytes += (size_t)(Z / 64) * 16 * 4;                       // reduction
-  return bytes;
+  size_t unit = 128 * 16;                                  // codewords
+  unit += (size_t)Z * (lds_levels > 2 ? lds_levels : 2) * 16;  // pp/stack
+  unit += (size_t)(Z / 64) * 16 * 4;                       // reduction
+  return (prf == PRF_AES128 ? AES_LDS_WORDS * 4 : 0) + K * unit;
 }
 
 // Grow-only per-device scratch for the global stack levels.  Reused
 // across launches; sized for the largest request seen.  NOTE: concurrent
 // fused/expand launches on DIFFERENT streams of one device would share
-// this buffer (workgroups with equal blockIdx of two kernels in flight
+// this buffer (units with equal index in two kernels in flight
 // overwrite each other's sibling stacks) — the python API serializes
 // launches per DPF call; servers that overlap launches across streams
 // pass a scratch buffer of their own per stream (eval_scratch_bytes).
@@ -1352,9 +1421,9 @@ uint4* get_scratch(size_t bytes, hipStream_t /*stream*/) {
   return reinterpret_cast<uint4*>(g_scratch[dev]);
 }
 
-// j-split: grow the grid to >= 1024 workgroups (4 per CU) so small
+// j-split: grow the launch to >= 1024 units (4 per CU) so small
 // batches still fill the chip; each extra split costs one targeted
-// descent (DS-1 pair expansions) per workgroup — negligible against
+// descent (DS-1 pair expansions) per unit — negligible against
 // pairs/2^slog leaf pairs.
 int eval_slog(int batch, int DS) {
   int slog = 0;
@@ -1363,8 +1432,46 @@ int eval_slog(int batch, int DS) {
   return slog;
 }
 
+// Units per workgroup (the kernel's K).  Only AES holds a table the units
+// of a workgroup can share, so every other PRF runs K = 1.  With the
+// 64 KiB table one AES workgroup is resident per CU whatever K is, so a
+// launch takes ceil(workgroups / CUs) rounds of K units each.  A round gets
+// cheaper per unit as K adds waves per SIMD, but not in proportion:
+// measured at n = 2^20, batch 512 on MI355X (profiles/PROFILING.md) a
+// round of 1/2/3/4 units takes 3.6/4.6/5.2/7.5 ms.  Take the K with the
+// cheapest rounds x cost, the smallest on ties: 2048 units -> K = 4 (2
+// rounds on 256 CUs); 1200 units -> K = 3; a single key's 256 segments ->
+// K = 1 (one unit on every CU).  GPUDPF_AES_UNITS=1..4 forces K, for A/B
+// runs and so that the tests reach every K; it is read at each launch (one
+// getenv) so a single process can compare them.
+int eval_units_per_wg(int prf, int n_units) {
+  if (prf != PRF_AES128) return 1;
+  if (const char* e = std::getenv("GPUDPF_AES_UNITS")) {
+    const int v = std::atoi(e);
+    if (v >= 1 && v <= AES_MAX_UNITS) return v;
+  }
+  int dev = 0, cus = 0;
+  HIP_CHECK(hipGetDevice(&dev));
+  HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount,
+                                  dev));
+  if (cus < 1) cus = 1;
+  static const int round_cost[AES_MAX_UNITS + 1] = {0, 36, 46, 52, 75};
+  int best = 1;
+  long best_cost = 0;
+  for (int k = 1; k <= AES_MAX_UNITS; ++k) {
+    const long wgs = (n_units + k - 1) / k;
+    const long cost = ((wgs + cus - 1) / cus) * round_cost[k];
+    if (k == 1 || cost < best_cost) {
+      best = k;
+      best_cost = cost;
+    }
+  }
+  return best;
+}
+
 // Bytes of global sibling-stack scratch one fused/expand launch touches:
-// one Z-wide uint4 row per workgroup and global stack level.
+// one Z-wide uint4 row per unit and global stack level (units index it,
+// so it does not depend on how units are grouped into workgroups).
 size_t eval_scratch_need(int batch, int depth, int zlog) {
   const int Z = 1 << zlog;
   const int DS = depth - zlog;
@@ -1382,13 +1489,16 @@ void launch_eval_t(const int* keys, const u32* table, u32* out,
   const int Z = 1 << zlog;
   const int DS = depth - zlog;
   const int slog = eval_slog(batch, DS);
-  const size_t shmem = fused_shmem_bytes(Z, DS, PRF);
-  auto kern = dpf_eval_kernel<PRF, FUSED>;
-  if (shmem > 65536) {
-    HIP_CHECK(hipFuncSetAttribute((const void*)kern,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)shmem));
+  const int n_units = batch << slog;
+  const int K = eval_units_per_wg(PRF, n_units);
+  const size_t shmem = fused_shmem_bytes(Z, DS, PRF, K);
+  auto kern = dpf_eval_kernel<PRF, FUSED, 1>;
+  if constexpr (PRF == PRF_AES128) {
+    if (K == 2) kern = dpf_eval_kernel<PRF, FUSED, 2>;
+    if (K == 3) kern = dpf_eval_kernel<PRF, FUSED, 3>;
+    if (K == 4) kern = dpf_eval_kernel<PRF, FUSED, 4>;
   }
+  if (shmem >= 65536) allow_large_lds((const void*)kern);
   // Caller-owned scratch (launches that may overlap on different streams
   // each bring their own) or the shared per-device buffer.
   const size_t need = eval_scratch_need(batch, depth, zlog);
@@ -1401,9 +1511,9 @@ void launch_eval_t(const int* keys, const u32* table, u32* out,
   } else {
     scratch = get_scratch(need, stream);
   }
-  hipLaunchKernelGGL(kern, dim3((unsigned)(batch << slog)), dim3((unsigned)Z),
-                     shmem, stream, keys, table, out, aes_tabs, scratch,
-                     depth, zlog, slog, n);
+  hipLaunchKernelGGL(kern, dim3((unsigned)((n_units + K - 1) / K)),
+                     dim3((unsigned)(K * Z)), shmem, stream, keys, table, out,
+                     aes_tabs, scratch, depth, zlog, slog, n_units, n);
   HIP_CHECK(hipGetLastError());
 }
 
