@@ -21,6 +21,14 @@ void launch_fused(std::uintptr_t keys, std::uintptr_t table, std::uintptr_t out,
                   std::uintptr_t scratch = 0, std::size_t scratch_bytes = 0);
 std::size_t eval_scratch_bytes(int batch, int depth, int zlog);
 
+// Launch geometry of launch_fused / launch_expand, for tests that assert
+// the regime they hit.  eval_slog: log2 of the per-key segment split
+// (j-split); pure host arithmetic, no HIP call.  eval_units_per_wg: the
+// (key, segment) units packed into one workgroup (1 unless prf is AES128);
+// honours GPUDPF_AES_UNITS and otherwise queries the current device.
+int eval_slog(int batch, int depth, int zlog);
+int eval_units_per_wg(int prf, int n_units);
+
 // Full expansion to low-32 one-hot shares, permuted row order
 //   out: device ptr, u32 [batch][n]  (row r = leaf_perm(idx))
 void launch_expand(std::uintptr_t keys, std::uintptr_t out,
@@ -87,7 +95,7 @@ void launch_gemm_u32_mfma(std::uintptr_t da, std::uintptr_t dbt,
 // Streaming mod-2^32 GEMM (gemm_stream.hip): reads the u32 table in place
 // (no transposed copy, no digit planes) — the huge-table wide-entry path.
 // a: [batch, K] u32 shares; b: [K, N] u32 table; c: [batch, N] u32
-// (zeroed by caller).  batch <= 64 (python wrapper chunks larger).
+// (zeroed by caller).  batch <= 16 (python wrapper chunks larger).
 void launch_gemm_u32_stream(std::uintptr_t a, std::uintptr_t b,
                             std::uintptr_t c, int batch, long long K,
                             long long N, std::uintptr_t stream);

@@ -1432,6 +1432,8 @@ int eval_slog(int batch, int DS) {
   return slog;
 }
 
+}  // namespace
+
 // Units per workgroup (the kernel's K).  Only AES holds a table the units
 // of a workgroup can share, so every other PRF runs K = 1.  With the
 // 64 KiB table one AES workgroup is resident per CU whatever K is, so a
@@ -1443,7 +1445,8 @@ int eval_slog(int batch, int DS) {
 // rounds on 256 CUs); 1200 units -> K = 3; a single key's 256 segments ->
 // K = 1 (one unit on every CU).  GPUDPF_AES_UNITS=1..4 forces K, for A/B
 // runs and so that the tests reach every K; it is read at each launch (one
-// getenv) so a single process can compare them.
+// getenv) so a single process can compare them.  Public (dpf_hip_api.h) so
+// the tests can assert which K a launch took.
 int eval_units_per_wg(int prf, int n_units) {
   if (prf != PRF_AES128) return 1;
   if (const char* e = std::getenv("GPUDPF_AES_UNITS")) {
@@ -1468,6 +1471,8 @@ int eval_units_per_wg(int prf, int n_units) {
   }
   return best;
 }
+
+namespace {
 
 // Bytes of global sibling-stack scratch one fused/expand launch touches:
 // one Z-wide uint4 row per unit and global stack level (units index it,
@@ -1551,6 +1556,12 @@ void launch_fused(std::uintptr_t keys, std::uintptr_t table, std::uintptr_t out,
                   std::uintptr_t scratch, std::size_t scratch_bytes) {
   launch_eval_dispatch<true>(keys, table, out, aes_tabs, batch, n, depth, zlog,
                              prf, stream, scratch, scratch_bytes);
+}
+
+int eval_slog(int batch, int depth, int zlog) {
+  if (batch <= 0 || zlog < 6 || zlog >= depth)
+    throw std::invalid_argument("bad batch/depth/zlog");
+  return eval_slog(batch, depth - zlog);
 }
 
 std::size_t eval_scratch_bytes(int batch, int depth, int zlog) {

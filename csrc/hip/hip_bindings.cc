@@ -66,6 +66,11 @@ PYBIND11_MODULE(_hip, m) {
         py::call_guard<py::gil_scoped_release>());
   m.def("eval_scratch_bytes", &gpudpf_hip::eval_scratch_bytes,
         py::arg("batch"), py::arg("depth"), py::arg("zlog"));
+  m.def("eval_slog",
+        static_cast<int (*)(int, int, int)>(&gpudpf_hip::eval_slog),
+        py::arg("batch"), py::arg("depth"), py::arg("zlog"));
+  m.def("eval_units_per_wg", &gpudpf_hip::eval_units_per_wg, py::arg("prf"),
+        py::arg("n_units"));
   m.def("eval_expand", &gpudpf_hip::launch_expand, py::arg("keys"),
         py::arg("out"), py::arg("aes_tabs"), py::arg("batch"), py::arg("n"),
         py::arg("depth"), py::arg("zlog"), py::arg("prf"), py::arg("stream"),
