@@ -15,7 +15,7 @@
 // generation is ITERATIVE (O(log n) PRF calls instead of the reference's
 // O(log^2 n) recursive re-evaluation), and the evaluation layout contract
 // (leaf_perm) is designed for the wave64 per-thread-DFS kernel in
-// csrc/hip/dpf_kernels.hip rather than the reference's Z-frontier DFS.
+// csrc/hip/dpf_eval.hip rather than the reference's Z-frontier DFS.
 
 #pragma once
 #include <cstdint>
@@ -85,6 +85,12 @@ void aes128_encrypt2_ni(const AesNiRoundKeys& rk, unsigned char out0[16],
 constexpr int kMaxDepth = 32;
 constexpr int kKeyInts = 524;   // serialized size in int32 (2096 bytes)
 constexpr int kEntryWords = 16; // table entry = 16 x u32 (padded)
+// Wire layout in int32 offsets (slot s = ints [4s, 4s+4)): correction word
+// cw[sel][level*2 + bit] is u128 slot 1 + sel*kCwPerSel + level*2 + bit.
+constexpr int kCwPerSel = 2 * kMaxDepth;  // correction words per selector
+constexpr int kKeyCwInt = 4;              // first correction-word int
+constexpr int kKeyRootInt = kKeyCwInt + 2 * kCwPerSel * 4;  // root seed (516)
+static_assert(kKeyRootInt + 2 * 4 == kKeyInts, "key = depth|cw|root|n");
 
 struct DpfKey {
   int depth = 0;          // log2(n)

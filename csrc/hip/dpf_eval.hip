@@ -1,0 +1,495 @@
+// MI355X (gfx950, CDNA4) HIP kernels for DPF expansion + fused PIR lookup.
+//
+// Design (MI355X-first, not a port — see SURVEY.md §7):
+//   * One UNIT of Z = 1<<zlog threads (Z = 256 = 4 wave64 for n >= 512)
+//     per (key, DFS segment); a 512-key batch is 2048 units.  A workgroup
+//     is one unit, except for AES, where up to four units form one
+//     workgroup and share the T-table (eval_units_per_wg).
+//   * Phase 1: breadth-first expansion of the GGM root to Z frontier seeds
+//     through an LDS ping-pong (zlog levels, ~2Z PRFs — negligible).
+//   * Phase 2: each thread owns ONE subtree and walks it with a sibling-
+//     stack DFS.  All threads execute the same DFS schedule => zero
+//     divergence, and the stack index is wave-uniform per step so LDS
+//     accesses are conflict-free b128 ops.  The two HOT stack levels
+//     (popped on 3/4 of all steps) live in registers; the cold remainder
+//     shares the phase-1 ping-pong LDS region (they are never live at the
+//     same time), keeping LDS small enough for 3-4 units per CU.
+//   * Each visited interior node expands BOTH children from one parent;
+//     for AES this shares one key schedule across the two encryptions
+//     (the reference re-expands per call: dpf_gpu/prf/prf.cu:159-184,
+//     flagged in its own TODO dpf.py:32-33).
+//   * Leaves: only the low 32 bits of a leaf share contribute to the
+//     (mod 2^32-truncated) output, because truncation is a ring hom of
+//     Z_2^128 -> Z_2^32.  The fused MAC is therefore 16 v_mad_u32 per leaf
+//     against u32 table rows — 16x less arithmetic and 4x less table
+//     traffic than the reference's mod-2^128 MAC (dpf_hybrid.cu:166-172),
+//     with bit-identical output.  Table loads are issued BEFORE the leaf
+//     PRFs of the same step, so ~1000 cycles of cipher work hides them.
+//   * AES T-table: a single 256-entry table replicated 64-way (byte
+//     entry*256 + (lane%64)*4, at LDS byte 0) so every lane reads its own
+//     LDS bank — measured 4.3x bank-conflict amplification with flat
+//     tables (SQ_LDS_BANK_CONFLICT 3.5e10 vs SQ_INSTS_LDS 8.1e9,
+//     profiles/) — and a lookup address is one v_perm_b32 of a state word.
+//     te1..te3 are byte rotations of te0 (1 v_alignbit per lookup) and
+//     sbox[x] = byte2 of te0[x], so one table serves the whole cipher;
+//     the five-term round sums are two 3-input xors (v_bitop3_b32).
+//   * Table layout: row(idx) = j<<(zlog+1) | t<<1 | b (leaf_perm in
+//     csrc/core/dpf_core.cc): at DFS step j the workgroup reads one
+//     contiguous 32 KB slab; every lane reads its two rows as 8 contiguous
+//     dwordx4 loads.  All workgroups stream the table in the same order
+//     => cross-key reuse in L2/LLC.
+//
+// This file holds the production DFS kernel and its launchers.  The device
+// PRFs are in prf_device.h; the naive / BFS / cooperative strategies in
+// dpf_strategies.hip; the speed-of-light and unit-test probes in
+// dpf_probes.hip.
+
+#include <hip/hip_runtime.h>
+
+#include <cstdlib>
+#include <stdexcept>
+
+#include "dpf_hip_api.h"
+#include "hip_util.h"
+#include "prf_device.h"
+
+namespace gpudpf_hip {
+
+GrowScratch g_eval_scratch;
+
+// DFS sibling-stack levels kept in LDS (deeper levels: registers;
+// shallower: global scratch)
+#define MAX_LDS_LEVELS 4
+// Most (key, segment) units one AES workgroup walks (they share the table)
+#define AES_MAX_UNITS 4
+
+// Geometry of one eval launch, the single statement of where every
+// sibling-stack level lives and how large the LDS and scratch slices are.
+// The kernel (indexing), the launcher (dynamic LDS size, scratch size) and
+// eval_scratch_bytes all read it.
+//
+// Sibling-stack placement by pop frequency (level d pops once per
+// 2^(DS-1-d) pairs): deepest two levels in registers, the next
+// MAX_LDS_LEVELS in LDS, the shallow remainder in global scratch
+// (touched <= 1/64 of steps) — keeping the per-unit LDS slice small
+// enough that four units fit beside the 64 KB AES table.
+struct EvalGeom {
+  int Z;            // threads per unit
+  int DS;           // subtree splits per thread (>= 1)
+  int lds_levels;   // stack levels [lds_base, DS-3] live in LDS
+  int lds_base;
+  int glob_levels;  // stack levels [1, lds_base-1] live in global scratch
+  int shared_u4;    // uint4s of the ping-pong / LDS-stack region of a unit
+  int unit_u32;     // u32s of one unit's LDS slice: cw | shared | red
+
+  __host__ __device__ EvalGeom(int depth, int zlog)
+      : Z(1 << zlog),
+        DS(depth - zlog),
+        lds_levels(DS > 3 ? (DS - 3 < MAX_LDS_LEVELS ? DS - 3 : MAX_LDS_LEVELS)
+                          : 0),
+        lds_base(DS - 2 - lds_levels),
+        // max(difference, 0), spelt so: from this form the compiler knows
+        // the 64-bit scratch row offset has a non-negative factor
+        glob_levels((DS - 3) - lds_levels > 0 ? (DS - 3) - lds_levels : 0),
+        shared_u4(Z * (lds_levels > 2 ? lds_levels : 2)),
+        unit_u32((2 * kCwPerSel + shared_u4) * 4 + (Z >> 6) * 16) {}
+
+  // u32s of LDS in front of the unit slices (the replicated AES table)
+  static __host__ __device__ constexpr int table_u32(int prf) {
+    return prf == PRF_AES128 ? AES_LDS_WORDS : 0;
+  }
+  // Dynamic LDS bytes of a workgroup of K units
+  std::size_t lds_bytes(int prf, int K) const {
+    return ((std::size_t)table_u32(prf) + (std::size_t)K * unit_u32) * 4;
+  }
+  // uint4s of global sibling-stack scratch in front of unit `unit`'s rows:
+  // one Z-wide row per unit and global level (units index it, so it does
+  // not depend on how units are grouped into workgroups)
+  __host__ __device__ std::size_t scratch_u4(int unit) const {
+    return (std::size_t)unit * glob_levels * Z;
+  }
+  // Scratch bytes a launch of n_units touches
+  std::size_t scratch_bytes(int n_units) const {
+    return scratch_u4(n_units) * sizeof(uint4);
+  }
+};
+
+template <int PRF>
+__device__ __forceinline__ void expand_pair(uint4 seed, int i,
+                                            const uint4* cw_lds,
+                                            const AesLds& T, uint4& c0,
+                                            uint4& c1) {
+  // Issue the correction-word reads BEFORE the PRF core: their address
+  // depends only on the seed parity, and the ~600-instruction cipher
+  // hides the LDS latency (left to itself the scheduler sinks them to
+  // +5 instructions before their wait — measured in the .s).
+  const int sel = (int)(seed.x & 1u);
+  uint4 cw0 = cw_lds[sel * kCwPerSel + i * 2 + 0];
+  uint4 cw1 = cw_lds[sel * kCwPerSel + i * 2 + 1];
+  uint4 p0, p1;
+  prf_pair<PRF>(seed, T, p0, p1);
+  c0 = add128(p0, cw0);
+  c1 = add128(p1, cw1);
+}
+
+// ---------------------------------------------------------------------------
+// Main kernel.  A UNIT is Z threads walking one (key, segment) pair; a
+// workgroup holds K units (K = 1 except for AES, where the K units share
+// one 64 KiB te0 table so the table does not cost occupancy).  Dynamic LDS
+// map (the kernel has no static LDS, so it starts at LDS byte 0):
+//   [aes: 0/16384 u32] then K unit slices of
+//   [cw: 128 uint4][shared: Z*max(2, min(DS-3, 4)) uint4][red: Z/64*16 u32]
+// The `shared` region is the phase-1 ping-pong (2*Z uint4) first, then the
+// cold DFS stack (LDS levels) — never live simultaneously.
+// Hot stack levels DS-1 / DS-2 are the registers rtop1 / rtop2.
+//
+// Multi-unit indexing: unit = blockIdx.x*K + threadIdx.x/Z, t = threadIdx.x
+// % Z.  Z is a multiple of 64, so a wave never straddles units and every
+// per-unit branch is wave-uniform.  Units never communicate: key, segment,
+// scratch row, cw/stack/red slices all index by unit, and partial sums
+// meet only in the wrapping atomics.  The workgroup barriers (staging,
+// the zlog phase-1 levels, the reduction) have trip counts that depend on
+// kernel arguments only; surplus units of the last workgroup (unit >=
+// n_units) join them but load no key or table data, write no scratch and
+// issue no atomics.
+// ---------------------------------------------------------------------------
+// slog: log2 of the DFS range split — each key's 2^(DS-1) leaf pairs are
+// divided over 2^slog units (j-split).  The split changes neither the
+// table layout nor the per-thread subtree assignment: unit (key, seg)
+// walks pairs [seg*P, (seg+1)*P) of every thread's subtree, paying one
+// extra targeted descent (DS-1 pair expansions) to enter at seg*P.  Fused
+// partials combine with wrapping u32 atomicAdd (exact mod 2^32).  This is
+// what fills 256 CUs at small batch (batch 512 alone = only 2 units/CU) and
+// doubles as the single-key low-latency mode (the reference needs a
+// separate cooperative-groups kernel for that: dpf_coop.cu).
+template <int PRF, bool FUSED, int K>
+__global__ __launch_bounds__(256 * K) void dpf_eval_kernel(
+    const int* __restrict__ keys, const u32* __restrict__ table,
+    u32* __restrict__ out, const u32* __restrict__ aes_tabs,
+    uint4* __restrict__ scratch, int depth, int zlog, int slog, int n_units,
+    long long n) {
+  extern __shared__ u32 smem[];
+  const EvalGeom g(depth, zlog);
+  const int Z = g.Z, DS = g.DS, lds_base = g.lds_base;
+  const int t = (int)threadIdx.x & (Z - 1);
+  const int u_local = K == 1 ? 0 : (int)threadIdx.x >> zlog;
+  const int unit = (int)blockIdx.x * K + u_local;
+  const bool active = unit < n_units;  // wave-uniform (Z % 64 == 0)
+  const int key_id = unit >> slog;
+  const int seg = unit & ((1 << slog) - 1);
+  const long long key_base = (long long)key_id * kKeyInts;
+
+  u32* unit_lds = smem + EvalGeom::table_u32(PRF) + u_local * g.unit_u32;
+  uint4* cw_lds = reinterpret_cast<uint4*>(unit_lds);  // 2 * kCwPerSel entries
+  uint4* shared_region = cw_lds + 2 * kCwPerSel;
+  u32* red = reinterpret_cast<u32*>(shared_region + g.shared_u4);
+  uint4* gstack = scratch + g.scratch_u4(unit);
+
+  // Stage codewords per unit; the AES te0 table once per workgroup.
+  if (active) {
+    for (int idx = t; idx < 2 * kCwPerSel; idx += Z)
+      cw_lds[idx] =
+          reinterpret_cast<const uint4*>(keys + key_base + kKeyCwInt)[idx];
+  }
+  if constexpr (PRF == PRF_AES128) aes_stage_table(smem, aes_tabs);
+  AesLds T{((u32)threadIdx.x & 63u) << 2};
+  uint4* pp = shared_region;
+  if (active && t == 0) {
+    const int* rp = keys + key_base + kKeyRootInt;
+    pp[0] = make_uint4((u32)rp[0], (u32)rp[1], (u32)rp[2], (u32)rp[3]);
+  }
+  __syncthreads();
+
+  // Phase 1: root -> Z frontier seeds (frontier position t has the
+  // first-consumed index bit as its MSB: t = bitrev(idx & (Z-1))).
+  uint4* a = pp;
+  uint4* b = pp + Z;
+  for (int l = 1; l <= zlog; ++l) {
+    const int i = depth - l;
+    if (active && t < (1 << l)) {
+      uint4 parent = a[t >> 1];
+      uint4 v = prf_full<PRF>(parent, (u32)(t & 1), T);
+      const int sel = (int)(parent.x & 1u);
+      b[t] = add128(v, cw_lds[sel * kCwPerSel + i * 2 + (t & 1)]);
+    }
+    __syncthreads();
+    uint4* tmp = a;
+    a = b;
+    b = tmp;
+  }
+  uint4 cur = a[t];
+  __syncthreads();  // everyone holds their frontier seed; pp is now free
+  uint4* stack = shared_region;  // LDS stack levels [lds_base, DS-3]
+
+  u32 acc[16];
+#pragma unroll
+  for (int w = 0; w < 16; ++w) acc[w] = 0;
+
+  if (active) {
+    // Targeted descent to leaf-pair j_lo: at split d take bit (DS-1-d) of
+    // j_lo, always recording the bit-1 child in the level's sibling slot
+    // (when the bit is 1 the slot is stale, but it is provably rewritten by
+    // a later descent before its next pop).
+    const long long pairs = 1LL << (DS - 1);
+    const long long j_lo = (long long)seg * (pairs >> slog);
+    const long long j_hi = j_lo + (pairs >> slog);
+    uint4 rtop1 = cur, rtop2 = cur;  // hot levels DS-1 / DS-2
+    for (int d = 1; d <= DS - 1; ++d) {
+      uint4 c0, c1;
+      expand_pair<PRF>(cur, DS - d, cw_lds, T, c0, c1);
+      if (d == DS - 1) rtop1 = c1;
+      else if (d == DS - 2) rtop2 = c1;
+      else if (d >= lds_base) stack[(d - lds_base) * Z + t] = c1;
+      else gstack[(size_t)(d - 1) * Z + t] = c1;
+      cur = ((j_lo >> (DS - 1 - d)) & 1) ? c1 : c0;
+    }
+
+    // leaf-level correction words (eval level 0) are read every iteration:
+    // hoist their low words into registers.  For AES, whose K = 4 kernel
+    // has 128 VGPRs to live in, into scalar ones: the values are the same
+    // for the whole unit, hence for the wave.
+    auto uni = [](u32 v) -> u32 {
+      if constexpr (PRF == PRF_AES128) return __builtin_amdgcn_readfirstlane(v);
+      else return v;
+    };
+    const u32 cwl[2][2] = {{uni(cw_lds[0].x), uni(cw_lds[1].x)},
+                           {uni(cw_lds[kCwPerSel].x),
+                            uni(cw_lds[kCwPerSel + 1].x)}};
+
+    for (long long j = j_lo; j < j_hi; ++j) {
+      // Issue the two table-row loads first: the leaf ciphers below hide
+      // their latency.
+      uint4 r0q[4], r1q[4];
+      if constexpr (FUSED) {
+        const uint4* rows =
+            reinterpret_cast<const uint4*>(table + ((j << (zlog + 1)) +
+                                                    ((long long)t << 1)) * 16);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          r0q[q] = rows[q];
+          r1q[q] = rows[q + 4];
+        }
+      }
+
+      u32 v0, v1;
+      {
+        u32 p0, p1;
+        prf_pair_low<PRF>(cur, T, p0, p1);
+        const int sel = (int)(cur.x & 1u);
+        v0 = p0 + cwl[sel][0];
+        v1 = p1 + cwl[sel][1];
+      }
+
+      if constexpr (FUSED) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          acc[4 * q + 0] += v0 * r0q[q].x + v1 * r1q[q].x;
+          acc[4 * q + 1] += v0 * r0q[q].y + v1 * r1q[q].y;
+          acc[4 * q + 2] += v0 * r0q[q].z + v1 * r1q[q].z;
+          acc[4 * q + 3] += v0 * r0q[q].w + v1 * r1q[q].w;
+        }
+      } else {
+        u32* orow = out + (u64)key_id * (u64)n +
+                    (u64)((j << (zlog + 1)) + ((long long)t << 1));
+        orow[0] = v0;
+        orow[1] = v1;
+      }
+
+      if (j + 1 == j_hi) break;
+      // Pop the deepest pending sibling (register-resident on 3/4 of steps)
+      // and descend its bit-0 spine.
+      const int c = (int)(__ffsll((unsigned long long)(j + 1)) - 1);
+      if (c == 0) {
+        cur = rtop1;
+        continue;  // next leaf-parent is the sibling itself
+      }
+      const int dpop = DS - 1 - c;
+      cur = (c == 1) ? rtop2
+            : (dpop >= lds_base) ? stack[(dpop - lds_base) * Z + t]
+                                 : gstack[(size_t)(dpop - 1) * Z + t];
+      for (int d = dpop + 1; d <= DS - 1; ++d) {
+        uint4 c0, c1;
+        expand_pair<PRF>(cur, DS - d, cw_lds, T, c0, c1);
+        if (d == DS - 1) rtop1 = c1;
+        else if (d == DS - 2) rtop2 = c1;
+        else if (d >= lds_base) stack[(d - lds_base) * Z + t] = c1;
+        else gstack[(size_t)(d - 1) * Z + t] = c1;
+        cur = c0;
+      }
+    }
+  }
+
+  if constexpr (FUSED) {
+    // Wave shfl reduction, then cross-wave sum through LDS.
+#pragma unroll
+    for (int w = 0; w < 16; ++w) {
+      u32 v = acc[w];
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+      acc[w] = v;
+    }
+    // (per unit: wave = the unit's own wave index, red = its own slice)
+    const int lane = t & 63, wave = t >> 6, nwaves = Z >> 6;
+    if (lane == 0) {
+#pragma unroll
+      for (int w = 0; w < 16; ++w) red[wave * 16 + w] = acc[w];
+    }
+    __syncthreads();
+    if (active && t < 16) {
+      u32 s = 0;
+      for (int wv = 0; wv < nwaves; ++wv) s += red[wv * 16 + t];
+      // Wrapping u32 atomic add combines the 2^slog segment partials
+      // exactly (mod 2^32); `out` is zeroed by the caller.
+      atomicAdd(&out[(u64)key_id * 16 + t], s);
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Host launchers
+// ---------------------------------------------------------------------------
+namespace {
+
+// j-split: grow the launch to >= 1024 units (4 per CU) so small
+// batches still fill the chip; each extra split costs one targeted
+// descent (DS-1 pair expansions) per unit — negligible against
+// pairs/2^slog leaf pairs.
+int slog_for(int batch, int DS) {
+  int slog = 0;
+  while ((batch << (slog + 1)) <= 2048 && slog + 2 <= DS - 1 && slog < 8)
+    ++slog;
+  return slog;
+}
+
+}  // namespace
+
+// Units per workgroup (the kernel's K).  Only AES holds a table the units
+// of a workgroup can share, so every other PRF runs K = 1.  With the
+// 64 KiB table one AES workgroup is resident per CU whatever K is, so a
+// launch takes ceil(workgroups / CUs) rounds of K units each.  A round gets
+// cheaper per unit as K adds waves per SIMD, but not in proportion:
+// measured at n = 2^20, batch 512 on MI355X (profiles/PROFILING.md) a
+// round of 1/2/3/4 units takes 3.6/4.6/5.2/7.5 ms.  Take the K with the
+// cheapest rounds x cost, the smallest on ties: 2048 units -> K = 4 (2
+// rounds on 256 CUs); 1200 units -> K = 3; a single key's 256 segments ->
+// K = 1 (one unit on every CU).  GPUDPF_AES_UNITS=1..4 forces K, for A/B
+// runs and so that the tests reach every K; it is read at each launch (one
+// getenv) so a single process can compare them.  Public (dpf_hip_api.h) so
+// the tests can assert which K a launch took.
+int eval_units_per_wg(int prf, int n_units) {
+  if (prf != PRF_AES128) return 1;
+  if (const char* e = std::getenv("GPUDPF_AES_UNITS")) {
+    const int v = std::atoi(e);
+    if (v >= 1 && v <= AES_MAX_UNITS) return v;
+  }
+  int dev = 0, cus = 0;
+  HIP_CHECK(hipGetDevice(&dev));
+  HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount,
+                                  dev));
+  if (cus < 1) cus = 1;
+  static const int round_cost[AES_MAX_UNITS + 1] = {0, 36, 46, 52, 75};
+  int best = 1;
+  long best_cost = 0;
+  for (int k = 1; k <= AES_MAX_UNITS; ++k) {
+    const long wgs = (n_units + k - 1) / k;
+    const long cost = ((wgs + cus - 1) / cus) * round_cost[k];
+    if (k == 1 || cost < best_cost) {
+      best = k;
+      best_cost = cost;
+    }
+  }
+  return best;
+}
+
+namespace {
+
+template <int PRF, bool FUSED>
+void launch_eval_t(const int* keys, const u32* table, u32* out,
+                   const u32* aes_tabs, int batch, long long n, int depth,
+                   int zlog, hipStream_t stream, uint4* own_scratch,
+                   size_t own_scratch_bytes) {
+  const EvalGeom g(depth, zlog);
+  const int slog = slog_for(batch, g.DS);
+  const int n_units = batch << slog;
+  const int K = eval_units_per_wg(PRF, n_units);
+  const size_t shmem = g.lds_bytes(PRF, K);
+  auto kern = dpf_eval_kernel<PRF, FUSED, 1>;
+  if constexpr (PRF == PRF_AES128) {
+    if (K == 2) kern = dpf_eval_kernel<PRF, FUSED, 2>;
+    if (K == 3) kern = dpf_eval_kernel<PRF, FUSED, 3>;
+    if (K == 4) kern = dpf_eval_kernel<PRF, FUSED, 4>;
+  }
+  if (shmem >= 65536) allow_large_lds((const void*)kern);
+  // Caller-owned scratch (launches that may overlap on different streams
+  // each bring their own: units with equal index in two kernels in flight
+  // would overwrite each other's sibling stacks) or the shared per-device
+  // buffer.
+  const size_t need = g.scratch_bytes(n_units);
+  uint4* scratch;
+  if (own_scratch) {
+    if (own_scratch_bytes < need)
+      throw std::invalid_argument("scratch buffer smaller than "
+                                  "eval_scratch_bytes(batch, depth, zlog)");
+    scratch = own_scratch;
+  } else {
+    scratch = static_cast<uint4*>(g_eval_scratch.get(need));
+  }
+  hipLaunchKernelGGL(kern, dim3((unsigned)((n_units + K - 1) / K)),
+                     dim3((unsigned)(K * g.Z)), shmem, stream, keys, table,
+                     out, aes_tabs, scratch, depth, zlog, slog, n_units, n);
+  HIP_CHECK(hipGetLastError());
+}
+
+template <bool FUSED>
+void launch_eval_dispatch(std::uintptr_t keys, std::uintptr_t table,
+                          std::uintptr_t out, std::uintptr_t aes_tabs,
+                          int batch, long long n, int depth, int zlog, int prf,
+                          std::uintptr_t stream, std::uintptr_t scratch,
+                          std::size_t scratch_bytes) {
+  if (batch <= 0) return;
+  if (depth < 1 || ((long long)1 << depth) != n)
+    throw std::invalid_argument("bad depth/n");
+  if (zlog < 6 || zlog >= depth)
+    throw std::invalid_argument("zlog must be in [6, depth)");
+  auto* k = reinterpret_cast<const int*>(keys);
+  auto* tb = reinterpret_cast<const u32*>(table);
+  auto* o = reinterpret_cast<u32*>(out);
+  auto* a = reinterpret_cast<const u32*>(aes_tabs);
+  auto s = reinterpret_cast<hipStream_t>(stream);
+  auto* sc = reinterpret_cast<uint4*>(scratch);
+  with_prf(prf, [&](auto P) {
+    launch_eval_t<decltype(P)::value, FUSED>(k, tb, o, a, batch, n, depth,
+                                             zlog, s, sc, scratch_bytes);
+  });
+}
+
+}  // namespace
+
+void launch_fused(std::uintptr_t keys, std::uintptr_t table, std::uintptr_t out,
+                  std::uintptr_t aes_tabs, int batch, long long n, int depth,
+                  int zlog, int prf, std::uintptr_t stream,
+                  std::uintptr_t scratch, std::size_t scratch_bytes) {
+  launch_eval_dispatch<true>(keys, table, out, aes_tabs, batch, n, depth, zlog,
+                             prf, stream, scratch, scratch_bytes);
+}
+
+int eval_slog(int batch, int depth, int zlog) {
+  if (batch <= 0 || zlog < 6 || zlog >= depth)
+    throw std::invalid_argument("bad batch/depth/zlog");
+  return slog_for(batch, depth - zlog);
+}
+
+std::size_t eval_scratch_bytes(int batch, int depth, int zlog) {
+  const int slog = eval_slog(batch, depth, zlog);  // validates the arguments
+  return EvalGeom(depth, zlog).scratch_bytes(batch << slog);
+}
+
+void launch_expand(std::uintptr_t keys, std::uintptr_t out,
+                   std::uintptr_t aes_tabs, int batch, long long n, int depth,
+                   int zlog, int prf, std::uintptr_t stream,
+                   std::uintptr_t scratch, std::size_t scratch_bytes) {
+  launch_eval_dispatch<false>(keys, /*table=*/0, out, aes_tabs, batch, n, depth,
+                              zlog, prf, stream, scratch, scratch_bytes);
+}
+
+}  // namespace gpudpf_hip

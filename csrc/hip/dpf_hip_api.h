@@ -1,5 +1,7 @@
-// Host-side API of the gpudpf HIP kernel library (implemented in
-// dpf_kernels.hip, bound to python in hip_bindings.cc).
+// Host-side API of the gpudpf HIP kernel library, bound to python in
+// hip_bindings.cc.  Implemented in dpf_eval.hip (fused / expand and their
+// geometry queries), dpf_strategies.hip (bfs / coop / naive), dpf_probes.hip
+// (prf_sol and the unit-test probes) and the three gemm files.
 #pragma once
 #include <cstddef>
 #include <cstdint>

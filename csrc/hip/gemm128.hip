@@ -13,14 +13,14 @@
 //     (A tile 16 KiB + B tile 16 KiB).
 // The mod-2^128 MAC cannot use MFMA (gfx950 integer matrix cores are
 // i8-input only); the MFMA path for the mod-2^32 PIR reduction lives in
-// gemm_u32 (see csrc/hip/dpf_kernels.hip fused MAC and SURVEY.md).
+// gemm_u32 (see csrc/hip/dpf_eval.hip fused MAC and SURVEY.md).
 
 #include <hip/hip_runtime.h>
 
 #include <stdexcept>
-#include <string>
 
 #include "dpf_hip_api.h"
+#include "hip_util.h"
 
 namespace gpudpf_hip {
 
@@ -29,14 +29,6 @@ namespace {
 using u32 = std::uint32_t;
 using u64 = std::uint64_t;
 using u128 = unsigned __int128;
-
-#define HIP_CHECK_G(expr)                                                 \
-  do {                                                                    \
-    hipError_t _e = (expr);                                               \
-    if (_e != hipSuccess)                                                 \
-      throw std::runtime_error(std::string("HIP error: ") +              \
-                               hipGetErrorString(_e));                   \
-  } while (0)
 
 struct u128v {
   u64 lo, hi;
@@ -124,13 +116,13 @@ void launch_gemm128(std::uintptr_t a, std::uintptr_t bt, std::uintptr_t c,
                      reinterpret_cast<const u128v*>(a),
                      reinterpret_cast<const u128v*>(bt),
                      reinterpret_cast<u128v*>(partials), M, N, K, kchunk);
-  HIP_CHECK_G(hipGetLastError());
+  HIP_CHECK(hipGetLastError());
   const long long MN = M * N;
   hipLaunchKernelGGL(gemm128_reduce_kernel,
                      dim3((unsigned)((MN + 255) / 256)), dim3(256), 0, s,
                      reinterpret_cast<const u128v*>(partials),
                      reinterpret_cast<u128v*>(c), MN, ksplit);
-  HIP_CHECK_G(hipGetLastError());
+  HIP_CHECK(hipGetLastError());
 }
 
 }  // namespace gpudpf_hip

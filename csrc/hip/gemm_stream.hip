@@ -40,25 +40,15 @@
 
 #include <hip/hip_runtime.h>
 
-#include <mutex>
 #include <stdexcept>
-#include <string>
 
 #include "dpf_hip_api.h"
+#include "hip_util.h"
 
 namespace gpudpf_hip {
 
 using u32 = std::uint32_t;
 using u64 = std::uint64_t;
-
-#define HIP_CHECK(expr)                                                   \
-  do {                                                                    \
-    hipError_t _e = (expr);                                               \
-    if (_e != hipSuccess)                                                 \
-      throw std::runtime_error(std::string("HIP error: ") +              \
-                               hipGetErrorString(_e) + " at " __FILE__   \
-                               ":" + std::to_string(__LINE__));          \
-  } while (0)
 
 namespace {
 
@@ -67,30 +57,10 @@ constexpr int kColsPerTile = 256;  // 64 lanes x 4 columns
 constexpr int kChunkK = 64;        // staged share rows per LDS refill
 constexpr int kMaxB = 16;          // accumulators = 4*B VGPRs per lane
 
-// Grow-only per-device partials scratch (kept alive forever so hipGraphs
-// capturing a launch stay valid — same policy as dpf_kernels.hip).
-// Shared across launches of one device: concurrent stream-GEMM launches
-// on DIFFERENT streams would race on it — the python API serializes
-// launches per call, which is the supported pattern (as with the DFS
-// scratch in dpf_kernels.hip).
-std::mutex g_part_mu;
-void* g_part[64] = {};
-size_t g_part_bytes[64] = {};
-
-u32* get_partials(size_t bytes) {
-  int dev = 0;
-  HIP_CHECK(hipGetDevice(&dev));
-  std::lock_guard<std::mutex> lock(g_part_mu);
-  if (g_part_bytes[dev] < bytes) {
-    size_t want = g_part_bytes[dev] ? g_part_bytes[dev] : bytes;
-    while (want < bytes) want *= 2;
-    void* p = nullptr;
-    HIP_CHECK(hipMalloc(&p, want));
-    g_part[dev] = p;  // old buffer intentionally retired (graph safety)
-    g_part_bytes[dev] = want;
-  }
-  return reinterpret_cast<u32*>(g_part[dev]);
-}
+// Per-segment partials scratch, with GrowScratch's sharing rule (hip_util.h):
+// stream-GEMM launches in flight on DIFFERENT streams of one device would
+// race on it; the python API serializes launches per call.
+GrowScratch g_partials;
 
 template <int B>
 __global__ __launch_bounds__(kThreads) void gemm_u32_stream_kernel(
@@ -249,7 +219,8 @@ void launch_b(const u32* a, const u32* b, u32* c, int batch, long long K,
   if (segs < 1) segs = 1;
   long long k_seg = ((K + segs - 1) / segs + kChunkK - 1) / kChunkK * kChunkK;
   segs = (K + k_seg - 1) / k_seg;
-  u32* part = get_partials((size_t)segs * batch * N * 4);
+  u32* part =
+      static_cast<u32*>(g_partials.get((size_t)segs * batch * N * 4));
   hipLaunchKernelGGL(gemm_u32_stream_kernel<B>,
                      dim3((unsigned)segs, (unsigned)col_tiles),
                      dim3(kThreads), 0, st, a, b, part, batch, K, N, k_seg,

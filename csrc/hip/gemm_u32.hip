@@ -22,9 +22,9 @@
 #include <hip/hip_runtime.h>
 
 #include <stdexcept>
-#include <string>
 
 #include "dpf_hip_api.h"
+#include "hip_util.h"
 
 namespace gpudpf_hip {
 
@@ -33,14 +33,6 @@ namespace {
 using u32 = std::uint32_t;
 using s8 = signed char;
 typedef int v4i __attribute__((ext_vector_type(4)));
-
-#define HIP_CHECK_U(expr)                                                 \
-  do {                                                                    \
-    hipError_t _e = (expr);                                               \
-    if (_e != hipSuccess)                                                 \
-      throw std::runtime_error(std::string("HIP error: ") +              \
-                               hipGetErrorString(_e));                   \
-  } while (0)
 
 // u32 -> four signed base-256 digits with borrow propagation.
 __global__ void digits_kernel(const u32* __restrict__ in,
@@ -130,7 +122,7 @@ void launch_digits(std::uintptr_t in, std::uintptr_t out, long long count,
   hipLaunchKernelGGL(digits_kernel, dim3((unsigned)blocks), dim3(256), 0, s,
                      reinterpret_cast<const u32*>(in),
                      reinterpret_cast<s8*>(out), count, count);
-  HIP_CHECK_U(hipGetLastError());
+  HIP_CHECK(hipGetLastError());
 }
 
 void launch_gemm_u32_mfma(std::uintptr_t da, std::uintptr_t dbt,
@@ -151,7 +143,7 @@ void launch_gemm_u32_mfma(std::uintptr_t da, std::uintptr_t dbt,
                      dim3(256), 0, s, reinterpret_cast<const s8*>(da),
                      reinterpret_cast<const s8*>(dbt),
                      reinterpret_cast<u32*>(c), M, N, K, kchunk);
-  HIP_CHECK_U(hipGetLastError());
+  HIP_CHECK(hipGetLastError());
 }
 
 }  // namespace gpudpf_hip

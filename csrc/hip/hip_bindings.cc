@@ -8,23 +8,14 @@
 
 #include <map>
 #include <mutex>
-#include <stdexcept>
-#include <string>
 
 #include "dpf_core.h"
 #include "dpf_hip_api.h"
+#include "hip_util.h"
 
 namespace py = pybind11;
 
 namespace {
-
-#define HIP_CHECK(expr)                                                    \
-  do {                                                                     \
-    hipError_t _e = (expr);                                                \
-    if (_e != hipSuccess)                                                  \
-      throw std::runtime_error(std::string("HIP error: ") +               \
-                               hipGetErrorString(_e));                    \
-  } while (0)
 
 // Per-device cached AES table buffer (5*256 u32: te0..te3, sbox).
 std::mutex g_aes_mu;
@@ -66,9 +57,8 @@ PYBIND11_MODULE(_hip, m) {
         py::call_guard<py::gil_scoped_release>());
   m.def("eval_scratch_bytes", &gpudpf_hip::eval_scratch_bytes,
         py::arg("batch"), py::arg("depth"), py::arg("zlog"));
-  m.def("eval_slog",
-        static_cast<int (*)(int, int, int)>(&gpudpf_hip::eval_slog),
-        py::arg("batch"), py::arg("depth"), py::arg("zlog"));
+  m.def("eval_slog", &gpudpf_hip::eval_slog, py::arg("batch"),
+        py::arg("depth"), py::arg("zlog"));
   m.def("eval_units_per_wg", &gpudpf_hip::eval_units_per_wg, py::arg("prf"),
         py::arg("n_units"));
   m.def("eval_expand", &gpudpf_hip::launch_expand, py::arg("keys"),

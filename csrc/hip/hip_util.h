@@ -1,0 +1,116 @@
+// Host-side helpers shared by the HIP translation units of gpudpf._hip:
+// error checking, the large-LDS opt-in, runtime -> compile-time PRF dispatch
+// and the grow-only device scratch.  Internal: not part of dpf_hip_api.h.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <mutex>
+#include <set>
+#include <stdexcept>
+#include <string>
+#include <type_traits>
+#include <utility>
+
+#include "dpf_core.h"
+
+#define HIP_CHECK(expr)                                                   \
+  do {                                                                    \
+    hipError_t _e = (expr);                                               \
+    if (_e != hipSuccess)                                                 \
+      throw std::runtime_error(std::string("HIP error: ") +              \
+                               hipGetErrorString(_e) + " at " __FILE__   \
+                               ":" + std::to_string(__LINE__));          \
+  } while (0)
+
+namespace gpudpf_hip {
+
+// The PRF ids and the key wire layout (dpf_core.h).
+using gpudpf::kCwPerSel;
+using gpudpf::kKeyCwInt;
+using gpudpf::kKeyInts;
+using gpudpf::kKeyRootInt;
+using gpudpf::PRF_AES128;
+using gpudpf::PRF_CHACHA20;
+using gpudpf::PRF_DUMMY;
+using gpudpf::PRF_SALSA20;
+
+// Launches that ask for 64 KiB or more of dynamic LDS (every kernel that
+// holds the replicated AES table) must raise the kernel's limit first.
+// Done once per (kernel, device), so a launch replayed or captured later
+// makes no runtime call beyond the launch itself.
+inline void allow_large_lds(const void* kern) {
+  static std::mutex mu;
+  static std::set<std::pair<const void*, int>> done;
+  int dev = 0;
+  HIP_CHECK(hipGetDevice(&dev));
+  std::lock_guard<std::mutex> lock(mu);
+  if (done.count({kern, dev})) return;
+  HIP_CHECK(hipFuncSetAttribute(
+      kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  done.insert({kern, dev});
+}
+
+// Runtime PRF id -> compile-time constant: calls f(std::integral_constant<
+// int, PRF>{}) for the matching PRF, so a launcher picks its kernel
+// instantiation with one generic lambda:
+//   with_prf(prf, [&](auto P) { launch(kernel<decltype(P)::value>); });
+template <class F>
+void with_prf(int prf, F&& f) {
+  switch (prf) {
+    case PRF_DUMMY: f(std::integral_constant<int, PRF_DUMMY>{}); break;
+    case PRF_SALSA20: f(std::integral_constant<int, PRF_SALSA20>{}); break;
+    case PRF_CHACHA20: f(std::integral_constant<int, PRF_CHACHA20>{}); break;
+    case PRF_AES128: f(std::integral_constant<int, PRF_AES128>{}); break;
+    default: throw std::invalid_argument("unknown PRF");
+  }
+}
+
+// Grow-only device scratch, one buffer per device, reused across launches
+// and sized for the largest request seen.  Growth is geometric (2x).
+//
+// An outgrown buffer is deliberately LEAKED, never freed: a hipGraph
+// captured while a launch used the old buffer holds its raw pointer and
+// replays against it, so freeing would turn later replays into
+// use-after-free.  With 2x growth the leaked memory stays below the live
+// buffer's size.
+//
+// The buffer is shared by every launch on a device that uses the same
+// instance: launches in flight on DIFFERENT streams would overwrite each
+// other.  The python API serializes launches per call; callers that
+// overlap launches across streams bring their own buffers.
+class GrowScratch {
+ public:
+  // At least `bytes` bytes on the current device (nullptr for 0 bytes).
+  void* get(std::size_t bytes) {
+    if (bytes == 0) return nullptr;
+    int dev = 0;
+    HIP_CHECK(hipGetDevice(&dev));
+    if (dev < 0 || dev >= kMaxDevices)
+      throw std::out_of_range("GrowScratch: no slot for device " +
+                              std::to_string(dev));
+    std::lock_guard<std::mutex> lock(mu_);
+    if (bytes_[dev] < bytes) {
+      std::size_t want = bytes_[dev] ? bytes_[dev] : bytes;
+      while (want < bytes) want *= 2;
+      void* p = nullptr;
+      HIP_CHECK(hipMalloc(&p, want));
+      ptr_[dev] = p;  // the old pointer is leaked on purpose, see above
+      bytes_[dev] = want;
+    }
+    return ptr_[dev];
+  }
+
+ private:
+  static constexpr int kMaxDevices = 64;
+  std::mutex mu_;
+  void* ptr_[kMaxDevices] = {};
+  std::size_t bytes_[kMaxDevices] = {};
+};
+
+// The one buffer behind the eval kernel's global sibling stack and the BFS
+// and cooperative frontiers (defined in dpf_eval.hip).  They share it
+// because BFS alone may ask for tens of GiB.
+extern GrowScratch g_eval_scratch;
+
+}  // namespace gpudpf_hip

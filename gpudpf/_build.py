@@ -73,7 +73,9 @@ def build_core(force=False):
 
 def build_hip(force=False):
     sources = [
-        os.path.join(CSRC, "hip", "dpf_kernels.hip"),
+        os.path.join(CSRC, "hip", "dpf_eval.hip"),
+        os.path.join(CSRC, "hip", "dpf_strategies.hip"),
+        os.path.join(CSRC, "hip", "dpf_probes.hip"),
         os.path.join(CSRC, "hip", "gemm128.hip"),
         os.path.join(CSRC, "hip", "gemm_u32.hip"),
         os.path.join(CSRC, "hip", "gemm_stream.hip"),

@@ -96,6 +96,23 @@ def test_lattice_enumerator_matches_launcher():
     assert sorted(out) == [(d, s) for d in range(16, 21) for s in range(d - 15)]
 
 
+def test_eval_scratch_bytes_matches_stack_placement():
+    """No GPU needed.  An independent statement of the scratch contract: of
+    the DS - 1 sibling-stack levels two live in registers, up to four in
+    LDS, and each of the rest takes one Z-wide row of 16-byte seeds per
+    (key, segment) unit."""
+    if _hip is None:
+        pytest.skip("gpudpf._hip cannot be imported")
+    for depth in range(7, 33):
+        zlog = _core.zlog_for_depth(depth)
+        ds, z = depth - zlog, 1 << zlog
+        for batch in (1, 3, 65, 512, 1025, 4096):
+            slog = _hip.eval_slog(batch, depth, zlog)
+            want = (batch << slog) * max(0, ds - 3 - 4) * z * 16
+            assert _hip.eval_scratch_bytes(batch, depth, zlog) == want, \
+                (depth, batch)
+
+
 @functools.lru_cache(maxsize=None)
 def _table(depth):
     n = 1 << depth
