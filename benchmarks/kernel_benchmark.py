@@ -55,33 +55,25 @@ def run(strategy, prf_name, n, batch, entry_size, reps, check=False):
     keys_gpu = keys_cpu.to(dev).contiguous()
     depth = n.bit_length() - 1
     stream = torch.cuda.current_stream(dev).cuda_stream
-    aes_ptr = dpf._aes_ptr
 
     def launch(b, keys_g):
         if strategy == "fused":
             out = torch.zeros((b, 16), dtype=torch.int32, device=dev)
-            _hip.eval_fused(keys_g.data_ptr(), dpf._table_gpu.data_ptr(),
-                            out.data_ptr(), aes_ptr, b, n, depth, dpf._zlog,
-                            prf, stream)
+            dpf._launch_fused(keys_g, out)
         elif strategy == "expand":
             out = torch.empty((b, n), dtype=torch.int32, device=dev)
-            _hip.eval_expand(keys_g.data_ptr(), out.data_ptr(), aes_ptr, b, n,
-                             depth, dpf._zlog, prf, stream)
+            dpf._launch_expand(keys_g, out)
         elif strategy == "naive":
             out = torch.empty((b, n), dtype=torch.int32, device=dev)
-            _hip.eval_naive(keys_g.data_ptr(), out.data_ptr(), aes_ptr, b, n,
-                            depth, prf, stream)
+            _hip.eval_naive(keys_g.data_ptr(), out.data_ptr(), dpf._aes_ptr,
+                            b, n, depth, prf, stream)
         elif strategy == "bfs":
             out = torch.empty((b, n), dtype=torch.int32, device=dev)
-            _hip.eval_bfs(keys_g.data_ptr(), out.data_ptr(), aes_ptr, b, n,
-                          depth, prf, stream)
+            dpf._launch_bfs(keys_g, out)
         elif strategy == "coop":
             out = torch.zeros((b, 16), dtype=torch.int32, device=dev)
             for i in range(b):
-                _hip.eval_coop(keys_g[i].data_ptr(),
-                               dpf._table_gpu.data_ptr(), out[i].data_ptr(),
-                               aes_ptr, n, depth, dpf._zlog, prf, True,
-                               stream)
+                dpf._launch_coop(keys_g[i], out[i], True)
         else:
             raise ValueError(strategy)
         return out

@@ -28,7 +28,7 @@ import torch
 import torch.distributed as td
 
 from gpudpf import _core
-from gpudpf.dpf import DPF
+from gpudpf.dpf import DPF, _as_index_tensor, as_key_batch
 
 
 class ShardedDPF(object):
@@ -96,8 +96,7 @@ class ShardedDPF(object):
         """Write natural GLOBAL-index rows; each rank keeps its residue
         class (idx %% W == rank) and ignores the rest, so every rank can
         be fed the same stream."""
-        idx = indices if isinstance(indices, torch.Tensor) \
-            else torch.as_tensor(indices, dtype=torch.int64)
+        idx = _as_index_tensor(indices)
         mine = (idx % self.world) == self.rank
         if not bool(mine.any()):
             return
@@ -106,8 +105,7 @@ class ShardedDPF(object):
     def table_read(self, indices):
         """Gather natural global rows owned by THIS rank (indices must
         all satisfy idx %% W == rank)."""
-        idx = indices if isinstance(indices, torch.Tensor) \
-            else torch.as_tensor(indices, dtype=torch.int64)
+        idx = _as_index_tensor(indices)
         if bool(((idx % self.world) != self.rank).any()):
             raise Exception("table_read: some indices belong to other ranks")
         return self.local.table_read(idx // self.world)
@@ -118,16 +116,9 @@ class ShardedDPF(object):
         Host-side (the restriction walks log2(W) PRF levels per key), one
         C++ call for the whole batch; on a serving path do this once per
         batch, then feed eval_gpu_into."""
-        if not isinstance(keys, torch.Tensor):
-            keys = torch.stack([k.reshape(-1) for k in keys])
-        if keys.dim() == 1:
-            keys = keys.unsqueeze(0)
         return torch.from_numpy(
-            _core.shard_subkey_batch(keys.contiguous().numpy(),
+            _core.shard_subkey_batch(as_key_batch(keys).numpy(),
                                      self.prf_method, self.rank, self.world))
-
-    # backwards-compatible internal alias
-    _subkeys = shard_subkeys
 
     def eval_gpu(self, keys, to_host=True):
         """Evaluate a batch of full-domain keys cooperatively.  Partials

@@ -4,6 +4,7 @@ without padding, GPU one-hot share output, runtime PRF choice per call
 path, >BATCH_SIZE batches in one launch)."""
 
 import os
+from functools import partial
 
 import numpy as np
 import torch
@@ -17,6 +18,37 @@ try:
 except ImportError:  # pragma: no cover - HIP runtime missing entirely
     _hip = None
     _HAS_HIP = False
+
+
+def as_key_batch(keys):
+    """A tensor ([524] or [b, 524]) or a list of key tensors as one
+    contiguous int32 [b, 524] CPU tensor.  Raises on any other dtype or
+    shape: nothing downstream may convert or broadcast keys."""
+    if isinstance(keys, torch.Tensor):
+        kt = keys.unsqueeze(0) if keys.dim() == 1 else keys
+    else:
+        kt = torch.stack([k.reshape(-1) for k in keys])
+    if (kt.dtype != torch.int32 or kt.dim() != 2
+            or kt.shape[1] != _core.KEY_INTS):
+        raise Exception("keys must be int32[%d] tensors (got %s%s)"
+                        % (_core.KEY_INTS, kt.dtype, list(kt.shape)))
+    return kt.cpu().contiguous()
+
+
+def _as_index_tensor(indices):
+    return indices if isinstance(indices, torch.Tensor) \
+        else torch.as_tensor(indices, dtype=torch.int64)
+
+
+def _check_arg(name, t, dev, dtype, shape):
+    """Launch-argument check: dtype, device, exact shape and contiguity.
+    Metadata only — safe under graph capture."""
+    if (t.dtype != dtype or t.device != dev or t.shape != shape
+            or not t.is_contiguous()):
+        raise Exception(
+            "%s must be a contiguous %s %s tensor on %s (got %s %s, strides "
+            "%s, on %s)" % (name, dtype, list(shape), dev, t.dtype,
+                            list(t.shape), list(t.stride()), t.device))
 
 
 class DPF(object):
@@ -142,6 +174,28 @@ class DPF(object):
             _core.leaf_perm_rows(indices.to(torch.int64).cpu().numpy(),
                                  self._n_domain, self._zlog))
 
+    def _rows(self, indices):
+        """Natural indices -> permuted table rows, as a device tensor."""
+        dev = self._table_gpu.device
+        if self._perm_gpu is not None:
+            return self._perm_gpu[indices.to(dev)]
+        return self._perm_rows(indices).to(dev)
+
+    def _alloc_table(self, dev):
+        """Zeroed device table, row permutation (when the domain is small
+        enough to materialize it) and AES tables for the set-up domain."""
+        nd = self._n_domain
+        self._table_gpu = torch.zeros((nd, self._entry_padded),
+                                      dtype=torch.int32, device=dev)
+        if nd <= self.PERM_MATERIALIZE_MAX:
+            self._perm_gpu = torch.from_numpy(
+                _core.leaf_perm_table(nd, self._zlog)).to(dev)
+        else:
+            self._perm_gpu = None
+        if self.prf_method == self.PRF_AES128:
+            self._aes_ptr = _hip.ensure_aes_tables(
+                self._table_gpu.device.index)
+
     def eval_init(self, table):
         """Upload an [n, e] int32 table.  n is padded to the next
         power-of-two domain (>= 128) and e to a multiple of 16; rows are
@@ -156,27 +210,15 @@ class DPF(object):
         n, e = int(table.shape[0]), int(table.shape[1])
         dev = self._setup_domain(n, e)
         if dev.type != "cuda":
-            self._table_gpu = None
-            self._perm_gpu = None
+            self.eval_free()
             return
-        nd, ep = self._n_domain, self._entry_padded
-        self._table_gpu = torch.zeros((nd, ep), dtype=torch.int32, device=dev)
-        if nd <= self.PERM_MATERIALIZE_MAX:
-            self._perm_gpu = torch.from_numpy(
-                _core.leaf_perm_table(nd, self._zlog)).to(dev)
-        else:
-            self._perm_gpu = None
+        self._alloc_table(dev)
         t32 = table.to(torch.int32)
-        rows_per_chunk = max(1, self.INIT_CHUNK_BYTES // (ep * 4))
+        rows_per_chunk = max(1, self.INIT_CHUNK_BYTES // (self._entry_padded * 4))
         for lo in range(0, n, rows_per_chunk):
             hi = min(n, lo + rows_per_chunk)
-            if self._perm_gpu is not None:
-                rows = self._perm_gpu[lo:hi]
-            else:
-                rows = self._perm_rows(torch.arange(lo, hi)).to(dev)
-            self._table_gpu[rows, :e] = t32[lo:hi].to(dev, non_blocking=False)
-        if self.prf_method == self.PRF_AES128:
-            self._aes_ptr = _hip.ensure_aes_tables(dev.index or 0)
+            self._table_gpu[self._rows(torch.arange(lo, hi)), :e] = \
+                t32[lo:hi].to(dev, non_blocking=False)
 
     def eval_init_empty(self, n, e):
         """Allocate a zeroed device table for an [n, e] domain WITHOUT host
@@ -187,15 +229,7 @@ class DPF(object):
         dev = self._setup_domain(n, e)
         if dev.type != "cuda":
             raise Exception("eval_init_empty requires a GPU device")
-        nd, ep = self._n_domain, self._entry_padded
-        self._table_gpu = torch.zeros((nd, ep), dtype=torch.int32, device=dev)
-        if nd <= self.PERM_MATERIALIZE_MAX:
-            self._perm_gpu = torch.from_numpy(
-                _core.leaf_perm_table(nd, self._zlog)).to(dev)
-        else:
-            self._perm_gpu = None
-        if self.prf_method == self.PRF_AES128:
-            self._aes_ptr = _hip.ensure_aes_tables(dev.index or 0)
+        self._alloc_table(dev)
 
     def table_write(self, indices, rows):
         """Streaming ingest: write natural-order rows [m, e] int32 at
@@ -205,26 +239,14 @@ class DPF(object):
         e = self.table_effective_entry_size
         if rows.dim() != 2 or int(rows.shape[1]) != e:
             raise Exception("rows must be [m, %d]" % e)
-        dev = self._table_gpu.device
-        idx = indices if isinstance(indices, torch.Tensor) \
-            else torch.as_tensor(indices, dtype=torch.int64)
-        if self._perm_gpu is not None:
-            prows = self._perm_gpu[idx.to(dev)]
-        else:
-            prows = self._perm_rows(idx).to(dev)
-        self._table_gpu[prows, :e] = rows.to(torch.int32).to(dev)
+        prows = self._rows(_as_index_tensor(indices))
+        self._table_gpu[prows, :e] = rows.to(torch.int32).to(prows.device)
 
     def table_read(self, indices):
         """Gather natural-order rows [m, e] int32 from the device table."""
         if self._table_gpu is None:
             raise Exception("call eval_init/eval_init_empty first")
-        dev = self._table_gpu.device
-        idx = indices if isinstance(indices, torch.Tensor) \
-            else torch.as_tensor(indices, dtype=torch.int64)
-        if self._perm_gpu is not None:
-            prows = self._perm_gpu[idx.to(dev)]
-        else:
-            prows = self._perm_rows(idx).to(dev)
+        prows = self._rows(_as_index_tensor(indices))
         return self._table_gpu[prows, : self.table_effective_entry_size]
 
     def eval_free(self):
@@ -232,14 +254,7 @@ class DPF(object):
         self._perm_gpu = None
 
     def _keys_tensor(self, keys):
-        if isinstance(keys, torch.Tensor):
-            kt = keys
-            if kt.dim() == 1:
-                kt = kt.unsqueeze(0)
-        else:
-            kt = torch.stack([k.reshape(-1) for k in keys])
-        if kt.dtype != torch.int32 or kt.shape[1] != self.KEY_INTS:
-            raise Exception("keys must be int32[524] tensors")
+        kt = as_key_batch(keys)
         # n is a u64 in u128 slot 130 (ints 520/521); depth is int 0.
         n = (int(kt[0, 521].item()) << 32) | (int(kt[0, 520].item()) & 0xFFFFFFFF)
         depth = int(kt[0, 0].item())
@@ -249,7 +264,83 @@ class DPF(object):
         if not bool((hdr == hdr[0]).all().item()):
             raise Exception("all keys in a batch must share one domain "
                             "(mixed depth/n header words)")
-        return kt.contiguous(), n, depth
+        return kt, n, depth
+
+    # ------------------------------------------------------------------
+    # Kernel launches: the only callers of _hip.eval_* in the package.
+    # They take tensors, check them against the table state (the kernels
+    # dereference whatever raw pointers they are handed) and launch on the
+    # table device's current stream.
+    # ------------------------------------------------------------------
+    def _launch_args(self, keys_gpu, key_shape, out_gpu, out_shape,
+                     scratch=None):
+        """Check one launch's arguments; returns (stream, scratch pointer,
+        scratch bytes).  Reads tensor metadata only (no sync, no copy, no
+        allocation), so it runs under graph capture and per serving step."""
+        if self._table_gpu is None:
+            raise Exception("table: call `eval_init` before evaluating")
+        dev = self._table_gpu.device
+        # the launchers' scratch and AES tables belong to the CURRENT device
+        if torch.cuda.current_device() != dev.index:
+            raise Exception("current device is cuda:%d but the table is on "
+                            "%s" % (torch.cuda.current_device(), dev))
+        _check_arg("keys", keys_gpu, dev, torch.int32, key_shape)
+        _check_arg("out", out_gpu, dev, torch.int32, out_shape)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        if scratch is None:
+            return stream, 0, 0  # the shared per-device scratch
+        _check_arg("scratch", scratch, dev, torch.uint8, (scratch.numel(),))
+        return stream, scratch.data_ptr(), scratch.numel()
+
+    def _scratch_bytes(self, batch):
+        """Sibling-stack scratch a fused/expand launch of `batch` keys
+        touches (0 for domains whose stack fits registers + LDS)."""
+        return _hip.eval_scratch_bytes(batch, self._depth, self._zlog)
+
+    def _launch_fused(self, keys_gpu, out_gpu, scratch=None):
+        """out_gpu [b,16] += the keys' table shares; the caller zeroes it
+        (the j-split segments accumulate with atomics).  Launches that can
+        be in flight together each need their own `scratch`."""
+        b = len(keys_gpu)
+        stream, sptr, sbytes = self._launch_args(
+            keys_gpu, (b, self.KEY_INTS), out_gpu, (b, self.ENTRY_SIZE),
+            scratch)
+        _hip.eval_fused(
+            keys_gpu.data_ptr(), self._table_gpu.data_ptr(),
+            out_gpu.data_ptr(), self._aes_ptr, b, self._n_domain,
+            self._depth, self._zlog, self.prf_method, stream, sptr, sbytes)
+
+    def _launch_expand(self, keys_gpu, shares_gpu, scratch=None):
+        """shares_gpu [b,n] = one-hot shares, rows in leaf_perm order."""
+        b = len(keys_gpu)
+        stream, sptr, sbytes = self._launch_args(
+            keys_gpu, (b, self.KEY_INTS), shares_gpu, (b, self._n_domain),
+            scratch)
+        _hip.eval_expand(
+            keys_gpu.data_ptr(), shares_gpu.data_ptr(), self._aes_ptr, b,
+            self._n_domain, self._depth, self._zlog, self.prf_method, stream,
+            sptr, sbytes)
+
+    def _launch_bfs(self, keys_gpu, shares_gpu):
+        """shares_gpu [b,n] = one-hot shares in NATURAL order (level-
+        synchronized breadth-first expansion, no un-permute gather)."""
+        b = len(keys_gpu)
+        stream, _, _ = self._launch_args(
+            keys_gpu, (b, self.KEY_INTS), shares_gpu, (b, self._n_domain))
+        _hip.eval_bfs(
+            keys_gpu.data_ptr(), shares_gpu.data_ptr(), self._aes_ptr, b,
+            self._n_domain, self._depth, self.prf_method, stream)
+
+    def _launch_coop(self, key_row, out_row, fused):
+        """One cooperative launch for one key [524]: out_row [16] += its
+        table share (caller zeroes) if fused, else out_row [n] = one-hot."""
+        stream, _, _ = self._launch_args(
+            key_row, (self.KEY_INTS,), out_row,
+            (self.ENTRY_SIZE if fused else self._n_domain,))
+        _hip.eval_coop(
+            key_row.data_ptr(), self._table_gpu.data_ptr(),
+            out_row.data_ptr(), self._aes_ptr, self._n_domain, self._depth,
+            self._zlog, self.prf_method, fused, stream)
 
     def eval_gpu(self, keys, one_hot_only=False, strategy="fused",
                  out_device=False):
@@ -269,77 +360,82 @@ class DPF(object):
             raise Exception("Must call `eval_init` before `eval_gpu`")
         if not _HAS_HIP:
             raise Exception("gpudpf._hip extension is not available")
-        kt, n, depth = self._keys_tensor(keys)
+        kt, n, _depth = self._keys_tensor(keys)
         if n != self._n_domain:
             raise Exception(
                 "key domain (%d) does not match table domain (%d)"
                 % (n, self._n_domain)
             )
+        keys_gpu = kt.to(self._table_gpu.device, non_blocking=True)
         if self._entry_padded > self.ENTRY_SIZE and not one_hot_only:
             strategy = "two_stage"  # wide entries go through the MFMA path
         if strategy == "two_stage" and not one_hot_only:
-            return self._eval_gpu_two_stage(kt, out_device=out_device)
-        if strategy == "coop":
-            return self._eval_gpu_coop(kt, n, depth, one_hot_only, out_device)
-        batch = kt.shape[0]
-        dev = self._table_gpu.device
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        keys_gpu = kt.to(dev, non_blocking=True)
-
-        results = []
-        for lo in range(0, batch, self.MAX_LAUNCH_BATCH):
-            hi = min(batch, lo + self.MAX_LAUNCH_BATCH)
-            chunk = keys_gpu[lo:hi].contiguous()
-            b = hi - lo
-            if one_hot_only:
-                out = torch.empty((b, n), dtype=torch.int32, device=dev)
-                if strategy == "bfs":
-                    # level-synchronized breadth-first expansion: writes
-                    # NATURAL-order rows directly (no un-permute gather)
-                    _hip.eval_bfs(
-                        chunk.data_ptr(), out.data_ptr(), self._aes_ptr, b,
-                        n, depth, self.prf_method, stream,
-                    )
-                else:
-                    if self._perm_gpu is None:
-                        raise Exception(
-                            "one_hot_only needs the materialized row "
-                            "permutation (domain > PERM_MATERIALIZE_MAX); "
-                            "use strategy='bfs' for natural-order output")
-                    _hip.eval_expand(
-                        chunk.data_ptr(), out.data_ptr(), self._aes_ptr, b,
-                        n, depth, self._zlog, self.prf_method, stream,
-                    )
-                    # rows are in leaf_perm order; gather back to natural
-                    # order and trim the power-of-two padding
-                    out = out.index_select(1, self._perm_gpu)
-                out = out[:, : self.table_num_entries]
+            res = self._eval_gpu_two_stage(keys_gpu)
+        else:
+            if strategy == "coop":
+                run = partial(self._eval_coop, fused=not one_hot_only)
+            elif one_hot_only:
+                run = partial(self._eval_one_hot, bfs=strategy == "bfs")
             else:
-                # zeroed: the kernel's j-split segments accumulate with atomics
-                out = torch.zeros((b, self.ENTRY_SIZE), dtype=torch.int32, device=dev)
-                _hip.eval_fused(
-                    chunk.data_ptr(), self._table_gpu.data_ptr(), out.data_ptr(),
-                    self._aes_ptr, b, n, depth, self._zlog, self.prf_method,
-                    stream,
-                )
-                out = out[:, : self.table_effective_entry_size]
-            results.append(out)
-        res = torch.cat(results) if len(results) > 1 else results[0]
+                run = self._eval_fused
+            outs = [run(keys_gpu[lo:lo + self.MAX_LAUNCH_BATCH])
+                    for lo in range(0, len(keys_gpu), self.MAX_LAUNCH_BATCH)]
+            res = torch.cat(outs) if len(outs) > 1 else outs[0]
+        # trim the power-of-two domain / 16-word entry padding
+        res = res[:, : self.table_num_entries if one_hot_only
+                  else self.table_effective_entry_size]
         return res if out_device else res.cpu()
 
-    def _eval_gpu_two_stage(self, keys, chunk=None, out_device=False):
+    def _new_out(self, b, one_hot):
+        """[b, n] uninitialized (one-hot kernels write every word) or
+        [b, 16] zeroed (fused kernels accumulate with atomics)."""
+        if one_hot:
+            return torch.empty((b, self._n_domain), dtype=torch.int32,
+                               device=self._table_gpu.device)
+        return torch.zeros((b, self.ENTRY_SIZE), dtype=torch.int32,
+                           device=self._table_gpu.device)
+
+    def _eval_fused(self, keys_gpu):
+        out = self._new_out(len(keys_gpu), one_hot=False)
+        self._launch_fused(keys_gpu, out)
+        return out
+
+    def _eval_one_hot(self, keys_gpu, bfs):
+        if not bfs and self._perm_gpu is None:
+            raise Exception(
+                "one_hot_only needs the materialized row permutation (domain "
+                "> PERM_MATERIALIZE_MAX); use strategy='bfs' for natural-order "
+                "output")
+        out = self._new_out(len(keys_gpu), one_hot=True)
+        if bfs:
+            self._launch_bfs(keys_gpu, out)
+            return out
+        self._launch_expand(keys_gpu, out)
+        # rows are in leaf_perm order; gather back to natural order
+        return out.index_select(1, self._perm_gpu)
+
+    def _eval_coop(self, keys_gpu, fused):
+        """Grid-wide cooperative strategy (the reference's dpf_coop.cu):
+        one cooperative launch per key, grid sync per tree level.  Kept
+        as a measured research strategy — the production j-split serves
+        the single-key-latency role without grid-wide synchronization."""
+        out = self._new_out(len(keys_gpu), one_hot=not fused)
+        for key_row, out_row in zip(keys_gpu, out):
+            self._launch_coop(key_row, out_row, fused)
+        return out
+
+    def _eval_gpu_two_stage(self, keys_gpu, chunk=None):
         """Expand one-hot shares (permuted rows), then reduce against the
         permuted table with the MFMA mod-2^32 GEMM — no gather needed
         because both sides share the leaf_perm row order.  Expansion of
         chunk i+1 overlaps the matmul of chunk i on two HIP streams (the
         reference's dual-stream expansion||GEMM pattern,
-        dpf_benchmark.cu:191-231)."""
+        dpf_benchmark.cu:191-231).  Returns the padded [b, ep] shares on
+        the device."""
         from gpudpf import ops
 
-        kt, n, depth = self._keys_tensor(keys)
         dev = self._table_gpu.device
-        keys_gpu = kt.to(dev, non_blocking=True).contiguous()
-        b = kt.shape[0]
+        b, n = len(keys_gpu), self._n_domain
         if chunk is None:
             # Bound the [chunk, n] one-hot share buffer by free HBM: two
             # chunks are alive at once (expand of i+1 overlaps matmul of
@@ -352,15 +448,18 @@ class DPF(object):
             chunk = max(1, min(128, int(budget // (n * 4))))
         s_expand = torch.cuda.Stream(dev)
         s_matmul = torch.cuda.Stream(dev)
+        # The expansion must follow the caller's stream: the key copy was
+        # issued there, and so was any earlier launch on the shared
+        # per-device scratch, which an overlapping expansion would
+        # overwrite (the hazard the pipelined servers avoid with per-slot
+        # scratch).
+        s_expand.wait_stream(torch.cuda.current_stream(dev))
         outs = []
         for lo in range(0, b, chunk):
             hi = min(b, lo + chunk)
             with torch.cuda.stream(s_expand):
                 shares = torch.empty((hi - lo, n), dtype=torch.int32, device=dev)
-                _hip.eval_expand(
-                    keys_gpu[lo:hi].contiguous().data_ptr(), shares.data_ptr(),
-                    self._aes_ptr, hi - lo, n, depth, self._zlog,
-                    self.prf_method, s_expand.cuda_stream)
+                self._launch_expand(keys_gpu[lo:hi], shares)
             s_matmul.wait_stream(s_expand)
             shares.record_stream(s_matmul)
             with torch.cuda.stream(s_matmul):
@@ -377,68 +476,20 @@ class DPF(object):
                         ops.pir_matmul_u32_stream(shares, self._table_gpu))
         torch.cuda.current_stream(dev).wait_stream(s_matmul)
         torch.cuda.current_stream(dev).wait_stream(s_expand)
-        out = torch.cat(outs) if len(outs) > 1 else outs[0]
-        out = out[:, : self.table_effective_entry_size]
-        return out if out_device else out.cpu()
-
-    def _eval_gpu_coop(self, kt, n, depth, one_hot_only, out_device):
-        """Grid-wide cooperative strategy (the reference's dpf_coop.cu):
-        one cooperative launch per key, grid sync per tree level.  Kept
-        as a measured research strategy — the production j-split serves
-        the single-key-latency role without grid-wide synchronization."""
-        dev = self._table_gpu.device
-        keys_gpu = kt.to(dev, non_blocking=True).contiguous()
-        b = kt.shape[0]
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        if one_hot_only:
-            out = torch.empty((b, n), dtype=torch.int32, device=dev)
-        else:
-            out = torch.zeros((b, self.ENTRY_SIZE), dtype=torch.int32,
-                              device=dev)
-        for i in range(b):
-            _hip.eval_coop(
-                keys_gpu[i].data_ptr(), self._table_gpu.data_ptr(),
-                out[i].data_ptr(), self._aes_ptr, n, depth, self._zlog,
-                self.prf_method, not one_hot_only, stream,
-            )
-        if one_hot_only:
-            out = out[:, : self.table_num_entries]
-        else:
-            out = out[:, : self.table_effective_entry_size]
-        return out if out_device else out.cpu()
+        return torch.cat(outs) if len(outs) > 1 else outs[0]
 
     def eval_gpu_into(self, keys_gpu, out_gpu):
         """Zero-copy serving path: keys already on device as [b,524] int32,
         fused result written into out_gpu [b,16] int32 asynchronously on the
         current stream (no host sync)."""
-        if self._table_gpu is None:
-            raise Exception("Must call `eval_init` before `eval_gpu_into`")
-        if (keys_gpu.dtype != torch.int32 or keys_gpu.dim() != 2
-                or keys_gpu.shape[1] != self.KEY_INTS):
-            raise Exception("keys_gpu must be int32[b, %d]" % self.KEY_INTS)
-        b = keys_gpu.shape[0]
-        if (out_gpu.dtype != torch.int32 or out_gpu.dim() != 2
-                or out_gpu.shape[0] != b
-                or out_gpu.shape[1] != self.ENTRY_SIZE):
-            raise Exception("out_gpu must be int32[%d, %d] (the kernel "
-                            "writes 16-word padded rows)"
-                            % (b, self.ENTRY_SIZE))
-        if not (keys_gpu.is_contiguous() and out_gpu.is_contiguous()):
-            raise Exception("keys_gpu/out_gpu must be contiguous")
         if os.environ.get("GPUDPF_DEBUG"):
             # optional (synchronizing) domain check for the serving path
-            _kt, n, _d = self._keys_tensor(keys_gpu.cpu())
+            _kt, n, _d = self._keys_tensor(keys_gpu)
             if n != self._n_domain:
-                raise Exception("key domain (%d) != table domain (%d)"
+                raise Exception("key domain (%s) != table domain (%s)"
                                 % (n, self._n_domain))
-        dev = self._table_gpu.device
-        stream = torch.cuda.current_stream(dev).cuda_stream
         out_gpu.zero_()  # j-split segments accumulate with atomics
-        _hip.eval_fused(
-            keys_gpu.data_ptr(), self._table_gpu.data_ptr(), out_gpu.data_ptr(),
-            self._aes_ptr, b, self._n_domain, self._depth, self._zlog,
-            self.prf_method, stream,
-        )
+        self._launch_fused(keys_gpu, out_gpu)
 
     def eval_cpu(self, keys, one_hot_only=False, num_threads=None):
         """CPU reference evaluation (O(n) PRF pairs per key; the reference's

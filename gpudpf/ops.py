@@ -3,11 +3,7 @@
 import torch
 
 from gpudpf import _core
-
-try:
-    from gpudpf import _hip
-except ImportError:  # pragma: no cover
-    _hip = None
+from gpudpf.dpf import _hip
 
 
 def gemm128(a, bt):
@@ -74,6 +70,8 @@ def pir_matmul_u32_stream(shares, table, out=None):
     b = table.to(dev).contiguous()
     c = out if out is not None else torch.empty(
         (M, N), dtype=torch.int32, device=dev)
+    assert (c.dtype == torch.int32 and c.shape == (M, N) and c.device == dev
+            and c.is_contiguous())
     stream = torch.cuda.current_stream(dev).cuda_stream
     for lo in range(0, M, 16):
         hi = min(M, lo + 16)

@@ -25,7 +25,94 @@ multi-launch wide path.
 
 import torch
 
-from gpudpf.dpf import DPF, _hip
+from gpudpf import ops
+from gpudpf.dpf import DPF, as_key_batch
+
+
+def _table_device(dpf):
+    if dpf._table_gpu is None:
+        raise Exception("eval_init the DPF before building a server")
+    return dpf._table_gpu.device
+
+
+class _Slot:
+    """Fixed-address buffers, stream and events of one in-flight batch.
+    `scratch` is the slot's own sibling-stack scratch (None: the shared
+    per-device buffer); `shares` exists on the wide (two-stage) paths."""
+
+    __slots__ = ("stream", "keys_pinned", "keys_gpu", "scratch", "shares",
+                 "out_gpu", "out_pinned", "graph", "expanded", "done", "busy")
+
+    def __init__(self, dpf, batch, stream=None, own_scratch=False,
+                 shares=False, out_pinned=False):
+        dev = dpf._table_gpu.device
+
+        def zeros(cols, **kw):
+            return torch.zeros((batch, cols), dtype=torch.int32, **kw)
+
+        self.stream = stream
+        self.keys_pinned = zeros(DPF.KEY_INTS).pin_memory()
+        self.keys_gpu = zeros(DPF.KEY_INTS, device=dev)
+        self.scratch = torch.empty(dpf._scratch_bytes(batch), dtype=torch.uint8,
+                                   device=dev) if own_scratch else None
+        self.shares = zeros(dpf._n_domain, device=dev) if shares else None
+        self.out_gpu = zeros(dpf._entry_padded, device=dev)
+        self.out_pinned = zeros(dpf._entry_padded).pin_memory() \
+            if out_pinned else None
+        self.graph = None
+        self.expanded = torch.cuda.Event()
+        self.done = torch.cuda.Event()
+        self.busy = False
+
+    def stage(self, keys):
+        """Checked [batch, 524] CPU keys -> keys_gpu, on the current
+        stream."""
+        # raw memcpy into the pinned staging buffer: torch's copy_ into a
+        # pinned tensor device-synchronizes when an async H2D from it is
+        # still pending (measured 5+ ms); numpy assignment does not.
+        self.keys_pinned.numpy()[:] = keys.numpy()
+        self.keys_gpu.copy_(self.keys_pinned, non_blocking=True)
+
+    def wait(self):
+        self.done.synchronize()
+        self.busy = False
+
+
+def _fixed_batch(srv, keys):
+    keys = as_key_batch(keys)
+    if keys.shape[0] != srv.batch:
+        raise Exception("%s is fixed at batch=%d"
+                        % (type(srv).__name__, srv.batch))
+    return keys
+
+
+def _take_slot(srv):
+    """Next slot of a pipelined server, round-robin; blocks only if the
+    slot's previous batch was never collected."""
+    slot = srv._slots[srv._next]
+    srv._next = (srv._next + 1) % srv.depth
+    if slot.busy:
+        slot.wait()
+    return slot
+
+
+def _capture(launch, dev, stream=None):
+    """Warm `launch` up on a side stream, then capture it into a graph."""
+    warm = torch.cuda.Stream(dev)
+    warm.wait_stream(torch.cuda.current_stream(dev))
+    with torch.cuda.stream(warm):
+        for _ in range(3):
+            launch()
+    torch.cuda.current_stream(dev).wait_stream(warm)
+    torch.cuda.synchronize(dev)
+    graph = torch.cuda.CUDAGraph()
+    # thread_local: the default 'global' capture mode errors ANY other
+    # thread's CUDA call during capture — under a nccl process group
+    # the RCCL watchdog thread races that window
+    with torch.cuda.graph(graph, stream=stream,
+                          capture_error_mode="thread_local"):
+        launch()
+    return graph
 
 
 class GraphedServer:
@@ -47,88 +134,44 @@ class GraphedServer:
         if hasattr(dpf, "local"):  # ShardedDPF
             self.sharded = dpf
             dpf = dpf.local
-        if dpf._table_gpu is None:
-            raise Exception("eval_init the DPF before building a server")
+        self.device = _table_device(dpf)
         self.dpf = dpf
         self.batch = batch
-        dev = dpf._table_gpu.device
-        self.device = dev
         self.wide = dpf._entry_padded > DPF.ENTRY_SIZE
         if self.sharded is not None and self.wide:
             raise Exception("sharded GraphedServer serves the fused path "
                             "(entry <= 16 words)")
-        self._keys_gpu = torch.zeros((batch, DPF.KEY_INTS), dtype=torch.int32,
-                                     device=dev)
-        self._keys_pinned = torch.zeros((batch, DPF.KEY_INTS),
-                                        dtype=torch.int32).pin_memory()
-        n = dpf._n_domain
-        ep = dpf._entry_padded
-        self._out_gpu = torch.zeros((batch, ep), dtype=torch.int32,
-                                    device=dev)
         if self.wide:
-            shares_bytes = batch * n * 4
+            shares_bytes = batch * dpf._n_domain * 4
             if shares_bytes > self.MAX_WIDE_SHARES_BYTES:
                 raise Exception(
                     "wide GraphedServer share buffer would need %d bytes "
                     "(> %d); lower the batch" %
                     (shares_bytes, self.MAX_WIDE_SHARES_BYTES))
-            self._shares_gpu = torch.zeros((batch, n), dtype=torch.int32,
-                                           device=dev)
+        # one step is in flight at a time: the shared scratch serves
+        slot = self._slot = _Slot(dpf, batch, shares=self.wide)
 
         def launch():
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            self._out_gpu.zero_()
             if self.wide:
-                _hip.eval_expand(self._keys_gpu.data_ptr(),
-                                 self._shares_gpu.data_ptr(), dpf._aes_ptr,
-                                 batch, n, dpf._depth, dpf._zlog,
-                                 dpf.prf_method, stream)
-                for lo in range(0, batch, 16):
-                    hi = min(batch, lo + 16)
-                    _hip.gemm_u32_stream(
-                        self._shares_gpu[lo:hi].data_ptr(),
-                        dpf._table_gpu.data_ptr(),
-                        self._out_gpu[lo:hi].data_ptr(), hi - lo, n, ep,
-                        stream)
+                dpf._launch_expand(slot.keys_gpu, slot.shares)
+                ops.pir_matmul_u32_stream(slot.shares, dpf._table_gpu,
+                                          out=slot.out_gpu)
             else:
-                _hip.eval_fused(self._keys_gpu.data_ptr(),
-                                dpf._table_gpu.data_ptr(),
-                                self._out_gpu.data_ptr(), dpf._aes_ptr,
-                                batch, n, dpf._depth, dpf._zlog,
-                                dpf.prf_method, stream)
+                slot.out_gpu.zero_()
+                dpf._launch_fused(slot.keys_gpu, slot.out_gpu)
 
-        # warm up on a side stream, then capture
-        s = torch.cuda.Stream(dev)
-        s.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(s):
-            for _ in range(3):
-                launch()
-        torch.cuda.current_stream(dev).wait_stream(s)
-        torch.cuda.synchronize(dev)
-        self._graph = torch.cuda.CUDAGraph()
-        # thread_local: the default 'global' capture mode errors ANY other
-        # thread's CUDA call during capture — under a nccl process group
-        # the RCCL watchdog thread races that window
-        with torch.cuda.graph(self._graph, capture_error_mode="thread_local"):
-            launch()
+        self._graph = _capture(launch, self.device)
 
     def eval(self, keys, to_host=True):
         """keys: [batch, 524] int32 CPU tensor (or list) — full-domain
         keys for a sharded server, which restricts them per rank.
         Returns [batch, e] shares (CPU by default)."""
-        if not isinstance(keys, torch.Tensor):
-            keys = torch.stack([k.reshape(-1) for k in keys])
+        keys = _fixed_batch(self, keys)
         if self.sharded is not None:
             keys = self.sharded.shard_subkeys(keys)
-        if keys.shape[0] != self.batch:
-            raise Exception("GraphedServer is fixed at batch=%d" % self.batch)
-        # raw memcpy into the pinned staging buffer: torch's copy_ into a
-        # pinned tensor device-synchronizes when an async H2D from it is
-        # still pending (measured 5+ ms); numpy assignment does not.
-        self._keys_pinned.numpy()[:] = keys.numpy()
-        self._keys_gpu.copy_(self._keys_pinned, non_blocking=True)
+        self._slot.stage(keys)
         self._graph.replay()
-        out = self._out_gpu
+        out = self._slot.out_gpu
         if self.sharded is not None:
             out = self.sharded._allreduce_(out)
         out = out[:, : self.dpf.table_effective_entry_size]
@@ -153,93 +196,49 @@ class PipelinedServer:
     """
 
     def __init__(self, dpf: DPF, batch: int, depth: int = 2):
-        if dpf._table_gpu is None:
-            raise Exception("eval_init the DPF before building a server")
+        self.device = _table_device(dpf)
         if dpf._entry_padded != DPF.ENTRY_SIZE:
             raise Exception("PipelinedServer serves the fused path "
                             "(entry <= 16 words)")
         self.dpf = dpf
         self.batch = batch
         self.depth = depth
-        dev = dpf._table_gpu.device
-        self.device = dev
-        n = dpf._n_domain
-        # Adjacent batches' kernels are in flight together on the slots'
-        # streams, so each slot owns its sibling-stack scratch: on the
-        # shared per-device buffer equal-numbered workgroups of the two
-        # kernels overwrite each other's stacks (n >= 2^16) and the shares
-        # come out wrong.
-        scratch_bytes = _hip.eval_scratch_bytes(batch, dpf._depth, dpf._zlog)
         self._slots = []
         for _ in range(depth):
-            slot = {
-                "stream": torch.cuda.Stream(dev),
-                "scratch": torch.empty(scratch_bytes, dtype=torch.uint8,
-                                       device=dev),
-                "keys_pinned": torch.zeros((batch, DPF.KEY_INTS),
-                                           dtype=torch.int32).pin_memory(),
-                "keys_gpu": torch.zeros((batch, DPF.KEY_INTS),
-                                        dtype=torch.int32, device=dev),
-                "out_gpu": torch.zeros((batch, DPF.ENTRY_SIZE),
-                                       dtype=torch.int32, device=dev),
-                "out_pinned": torch.zeros((batch, DPF.ENTRY_SIZE),
-                                          dtype=torch.int32).pin_memory(),
-                "event": torch.cuda.Event(),
-                "busy": False,
-            }
+            # Adjacent batches' kernels are in flight together on the
+            # slots' streams, so each slot owns its sibling-stack scratch:
+            # on the shared per-device buffer equal-numbered workgroups of
+            # the two kernels overwrite each other's stacks (n >= 2^16)
+            # and the shares come out wrong.
+            slot = _Slot(dpf, batch, stream=torch.cuda.Stream(self.device),
+                         own_scratch=True, out_pinned=True)
 
             def launch(s=slot):
-                stream = torch.cuda.current_stream(dev).cuda_stream
-                s["out_gpu"].zero_()
-                _hip.eval_fused(s["keys_gpu"].data_ptr(),
-                                dpf._table_gpu.data_ptr(),
-                                s["out_gpu"].data_ptr(), dpf._aes_ptr, batch,
-                                n, dpf._depth, dpf._zlog, dpf.prf_method,
-                                stream, s["scratch"].data_ptr(),
-                                scratch_bytes)
+                s.out_gpu.zero_()
+                dpf._launch_fused(s.keys_gpu, s.out_gpu, s.scratch)
 
-            warm =torch.cuda.Stream(dev)
-            warm.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(warm):
-                for _ in range(3):
-                    launch()
-            torch.cuda.current_stream(dev).wait_stream(warm)
-            torch.cuda.synchronize(dev)
-            slot["graph"] = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(slot["graph"], stream=slot["stream"],
-                                  capture_error_mode="thread_local"):
-                launch()
+            slot.graph = _capture(launch, self.device, stream=slot.stream)
             self._slots.append(slot)
         self._next = 0
 
     def submit(self, keys):
         """Stage + launch a batch on the next slot (blocks only if the
         slot's previous batch has not been collected)."""
-        if not isinstance(keys, torch.Tensor):
-            keys = torch.stack([k.reshape(-1) for k in keys])
-        if keys.shape[0] != self.batch:
-            raise Exception("PipelinedServer is fixed at batch=%d"
-                            % self.batch)
-        slot = self._slots[self._next]
-        self._next = (self._next + 1) % self.depth
-        if slot["busy"]:
-            slot["event"].synchronize()  # previous user never collected
-            slot["busy"] = False
-        slot["keys_pinned"].numpy()[:] = keys.numpy()
-        with torch.cuda.stream(slot["stream"]):
-            slot["keys_gpu"].copy_(slot["keys_pinned"], non_blocking=True)
-            slot["graph"].replay()
-            slot["out_pinned"].copy_(slot["out_gpu"], non_blocking=True)
-            slot["event"].record(slot["stream"])
-        slot["busy"] = True
+        keys = _fixed_batch(self, keys)
+        slot = _take_slot(self)
+        with torch.cuda.stream(slot.stream):
+            slot.stage(keys)
+            slot.graph.replay()
+            slot.out_pinned.copy_(slot.out_gpu, non_blocking=True)
+            slot.done.record(slot.stream)
+        slot.busy = True
         return slot
 
     def collect(self, slot):
         """Wait for a submitted batch and return its [batch, e] shares."""
-        slot["event"].synchronize()
-        slot["busy"] = False
-        return slot["out_pinned"][:, : self.dpf.table_effective_entry_size
-                                  ].clone()
+        slot.wait()
+        return slot.out_pinned[:, : self.dpf.table_effective_entry_size
+                               ].clone()
 
 
 class TwoStageServer:
@@ -257,8 +256,7 @@ class TwoStageServer:
     """
 
     def __init__(self, dpf: DPF, batch: int, depth: int = 2):
-        if dpf._table_gpu is None:
-            raise Exception("eval_init the DPF before building a server")
+        dev = self.device = _table_device(dpf)
         if dpf._entry_padded <= DPF.ENTRY_SIZE:
             raise Exception("TwoStageServer serves wide entries "
                             "(> 16 words); use PipelinedServer")
@@ -268,79 +266,37 @@ class TwoStageServer:
         self.dpf = dpf
         self.batch = batch
         self.depth = depth
-        dev = dpf._table_gpu.device
-        self.device = dev
-        n = dpf._n_domain
-        ep = dpf._entry_padded
         free, _total = torch.cuda.mem_get_info(dev)
-        need = depth * batch * n * 4
+        need = depth * batch * dpf._n_domain * 4
         if need > free - (2 << 30):
             raise Exception("pipeline share buffers need %d bytes "
                             "(free %d); lower batch/depth" % (need, free))
         self._gemm_stream = torch.cuda.Stream(dev)
         # expansions of adjacent batches can overlap on the slots' streams:
         # per-slot sibling-stack scratch (see PipelinedServer)
-        self._scratch_bytes = _hip.eval_scratch_bytes(batch, dpf._depth,
-                                                      dpf._zlog)
-        self._slots = []
-        for _ in range(depth):
-            self._slots.append({
-                "stream": torch.cuda.Stream(dev),
-                "scratch": torch.empty(self._scratch_bytes,
-                                       dtype=torch.uint8, device=dev),
-                "keys_pinned": torch.zeros((batch, DPF.KEY_INTS),
-                                           dtype=torch.int32).pin_memory(),
-                "keys_gpu": torch.zeros((batch, DPF.KEY_INTS),
-                                        dtype=torch.int32, device=dev),
-                "shares": torch.zeros((batch, n), dtype=torch.int32,
-                                      device=dev),
-                "out_gpu": torch.zeros((batch, ep), dtype=torch.int32,
-                                       device=dev),
-                "ev_expand": torch.cuda.Event(),
-                "ev_done": torch.cuda.Event(),
-                "busy": False,
-            })
+        self._slots = [_Slot(dpf, batch, stream=torch.cuda.Stream(dev),
+                             own_scratch=True, shares=True)
+                       for _ in range(depth)]
         self._next = 0
 
     def submit(self, keys):
-        if not isinstance(keys, torch.Tensor):
-            keys = torch.stack([k.reshape(-1) for k in keys])
-        if keys.shape[0] != self.batch:
-            raise Exception("TwoStageServer is fixed at batch=%d"
-                            % self.batch)
-        dpf = self.dpf
-        slot = self._slots[self._next]
-        self._next = (self._next + 1) % self.depth
-        if slot["busy"]:
-            slot["ev_done"].synchronize()
-            slot["busy"] = False
-        slot["keys_pinned"].numpy()[:] = keys.numpy()
-        n = dpf._n_domain
-        with torch.cuda.stream(slot["stream"]):
-            slot["keys_gpu"].copy_(slot["keys_pinned"], non_blocking=True)
-            _hip.eval_expand(slot["keys_gpu"].data_ptr(),
-                             slot["shares"].data_ptr(), dpf._aes_ptr,
-                             self.batch, n, dpf._depth, dpf._zlog,
-                             dpf.prf_method, slot["stream"].cuda_stream,
-                             slot["scratch"].data_ptr(), self._scratch_bytes)
-            slot["ev_expand"].record(slot["stream"])
+        keys = _fixed_batch(self, keys)
+        slot = _take_slot(self)
+        with torch.cuda.stream(slot.stream):
+            slot.stage(keys)
+            self.dpf._launch_expand(slot.keys_gpu, slot.shares, slot.scratch)
+            slot.expanded.record(slot.stream)
         # the GEMM stream serializes table passes across slots (the table
         # stream is the contended resource); it only waits for THIS
         # slot's expansion
-        self._gemm_stream.wait_event(slot["ev_expand"])
+        self._gemm_stream.wait_event(slot.expanded)
         with torch.cuda.stream(self._gemm_stream):
-            slot["out_gpu"].zero_()
-            _hip.gemm_u32_stream(slot["shares"].data_ptr(),
-                                 dpf._table_gpu.data_ptr(),
-                                 slot["out_gpu"].data_ptr(), self.batch, n,
-                                 dpf._entry_padded,
-                                 self._gemm_stream.cuda_stream)
-            slot["ev_done"].record(self._gemm_stream)
-        slot["busy"] = True
+            ops.pir_matmul_u32_stream(slot.shares, self.dpf._table_gpu,
+                                      out=slot.out_gpu)
+            slot.done.record(self._gemm_stream)
+        slot.busy = True
         return slot
 
     def collect(self, slot):
-        slot["ev_done"].synchronize()
-        slot["busy"] = False
-        return slot["out_gpu"][:, : self.dpf.table_effective_entry_size
-                               ].cpu()
+        slot.wait()
+        return slot.out_gpu[:, : self.dpf.table_effective_entry_size].cpu()

@@ -155,6 +155,50 @@ def test_large_domain_header_decode():
     assert n == 1 << 32 and depth == 32
 
 
+def test_as_key_batch_accepts_list_row_and_batch():
+    from gpudpf.dpf import as_key_batch
+
+    d = DPF(prf=DPF.PRF_SALSA20, device="cpu")
+    k1s, _ = d.gen_batch([1, 2, 3], 1024)
+    strided = torch.stack([k1s, k1s], dim=1)[:, 0]  # non-contiguous view
+    assert not strided.is_contiguous()
+    for given in ([k1s[0], k1s[1], k1s[2]], k1s, strided):
+        kt = as_key_batch(given)
+        assert kt.dtype == torch.int32 and kt.shape == (3, 524)
+        assert kt.is_contiguous() and kt.device.type == "cpu"
+        assert torch.equal(kt, k1s)
+    one = as_key_batch(k1s[1])
+    assert one.shape == (1, 524) and torch.equal(one[0], k1s[1])
+
+
+@pytest.mark.parametrize("bad", [
+    torch.zeros((2, 524), dtype=torch.int64),
+    torch.zeros((2, 523), dtype=torch.int32),
+    torch.zeros((2, 1, 524), dtype=torch.int32),
+    [torch.zeros(524, dtype=torch.int64)],
+    [torch.zeros(523, dtype=torch.int32)],
+], ids=["int64", "width523", "3d", "list-int64", "list-width523"])
+def test_as_key_batch_rejects(bad):
+    from gpudpf.dpf import as_key_batch
+
+    with pytest.raises(Exception, match="keys must be int32"):
+        as_key_batch(bad)
+
+
+def test_keys_tensor_triple_and_mixed_domains():
+    d = DPF(prf=DPF.PRF_SALSA20, device="cpu")
+    k1s, _ = d.gen_batch([5, 6], 1000)  # 1024-entry domain
+    for given in (k1s, [k1s[0], k1s[1]]):
+        kt, n, depth = d._keys_tensor(given)
+        assert torch.equal(kt, k1s) and kt.is_contiguous()
+        assert (n, depth) == (1024, 10)
+    other, _ = d.gen(5, 2048)
+    with pytest.raises(Exception, match="domain"):
+        d._keys_tensor([k1s[0], other])
+    with pytest.raises(Exception, match="keys must be int32"):
+        d._keys_tensor(k1s.to(torch.int64))
+
+
 def test_compact_key_round_trip():
     d = DPF(prf=DPF.PRF_CHACHA20, device="cpu")
     for n, depth in ((128, 7), (1 << 14, 14)):
