@@ -5,6 +5,7 @@
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <utility>
 
 namespace gpudpf_hip {
 
@@ -88,6 +89,12 @@ void launch_gemm128(std::uintptr_t a, std::uintptr_t bt, std::uintptr_t c,
 // MFMA mod-2^32 GEMM (gemm_u32.hip): digit decomposition + i8 matrix
 // cores.  da/dbt: [4][M][K] / [4][N][K] int8 digit planes; c: [M][N] u32
 // (zeroed by caller; K-split partials combine with wrapping atomicAdd).
+// gemm_u32_split: the launcher's (ksplit, kchunk) — blockIdx.z slices of
+// kchunk (a multiple of 64) that together cover K; pure host arithmetic,
+// no HIP call.  Throws std::invalid_argument unless M%64, N%16 and K%64
+// are all 0.
+std::pair<long long, long long> gemm_u32_split(long long M, long long N,
+                                               long long K);
 void launch_digits(std::uintptr_t in, std::uintptr_t out, long long count,
                    std::uintptr_t stream);
 void launch_gemm_u32_mfma(std::uintptr_t da, std::uintptr_t dbt,

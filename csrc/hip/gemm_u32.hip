@@ -22,6 +22,7 @@
 #include <hip/hip_runtime.h>
 
 #include <stdexcept>
+#include <utility>
 
 #include "dpf_hip_api.h"
 #include "hip_util.h"
@@ -125,17 +126,29 @@ void launch_digits(std::uintptr_t in, std::uintptr_t out, long long count,
   HIP_CHECK(hipGetLastError());
 }
 
-void launch_gemm_u32_mfma(std::uintptr_t da, std::uintptr_t dbt,
-                          std::uintptr_t c, long long M, long long N,
-                          long long K, std::uintptr_t stream) {
-  if (M % 64 || N % 16 || K % 64)
+std::pair<long long, long long> gemm_u32_split(long long M, long long N,
+                                               long long K) {
+  if (M <= 0 || N <= 0 || K <= 0 || M % 64 || N % 16 || K % 64)
     throw std::invalid_argument("gemm_u32: M%64, N%16, K%64 must be 0");
+  // fill ~1024 workgroups; ksplit is a power of two, K-chunks are whole
+  // 64-deep MFMA steps
   long long xy = (M / 64) * (N / 16);
   long long want = (1024 + xy - 1) / xy;
   long long maxs = K / 64;
   long long ks = 1;
   while (ks * 2 <= want && ks * 2 <= maxs) ks *= 2;
-  long long kchunk = ((K / ks) + 63) / 64 * 64;
+  // ceil on both divisions: with floor(K / ks) the slices stop short of K
+  // whenever floor(K / ks) is a multiple of 64 and ks does not divide K.
+  // Slices that start at or past K add zero.
+  long long kchunk = ((K + ks - 1) / ks + 63) / 64 * 64;
+  return {ks, kchunk};
+}
+
+void launch_gemm_u32_mfma(std::uintptr_t da, std::uintptr_t dbt,
+                          std::uintptr_t c, long long M, long long N,
+                          long long K, std::uintptr_t stream) {
+  const auto split = gemm_u32_split(M, N, K);
+  const long long ks = split.first, kchunk = split.second;
   auto s = reinterpret_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(gemm_u32_mfma_kernel,
                      dim3((unsigned)(M / 64), (unsigned)(N / 16),

@@ -5,6 +5,7 @@
 
 #include <hip/hip_runtime.h>
 #include <pybind11/pybind11.h>
+#include <pybind11/stl.h>
 
 #include <map>
 #include <mutex>
@@ -92,6 +93,8 @@ PYBIND11_MODULE(_hip, m) {
   m.def("gemm_u32_mfma", &gpudpf_hip::launch_gemm_u32_mfma, py::arg("da"),
         py::arg("dbt"), py::arg("c"), py::arg("m"), py::arg("n"), py::arg("k"),
         py::arg("stream"), py::call_guard<py::gil_scoped_release>());
+  m.def("gemm_u32_split", &gpudpf_hip::gemm_u32_split, py::arg("m"),
+        py::arg("n"), py::arg("k"));
   m.def("gemm_u32_stream", &gpudpf_hip::launch_gemm_u32_stream, py::arg("a"),
         py::arg("b"), py::arg("c"), py::arg("batch"), py::arg("k"),
         py::arg("n"), py::arg("stream"),
