@@ -46,6 +46,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cstdint>
 #include <cstdlib>
 #include <stdexcept>
 
@@ -162,12 +163,25 @@ __device__ __forceinline__ void expand_pair(uint4 seed, int i,
 // what fills 256 CUs at small batch (batch 512 alone = only 2 units/CU) and
 // doubles as the single-key low-latency mode (the reference needs a
 // separate cooperative-groups kernel for that: dpf_coop.cu).
-template <int PRF, bool FUSED, int K>
+//
+// BINNED (batch PIR): `table` is num_bins consecutive blocks of n rows, each
+// in leaf_perm(n, zlog) order, and key i walks block bins[i].  Only the row
+// base differs; the id is loaded once per unit and made scalar, so the base
+// stays in SGPRs and the per-step row address stays scalar base + vector
+// offset.  n is then the rows of ONE block.  The ids (int32 [batch], each in
+// [0, num_bins)) arrive as an argument pack that is empty for the unbinned
+// instantiations: an argument of any type, even an empty struct, would move
+// their hidden kernel arguments and change their code.
+__device__ __forceinline__ const int* bin_ids(const int* ids) { return ids; }
+
+template <int PRF, bool FUSED, int K, class... Bins>
 __global__ __launch_bounds__(256 * K) void dpf_eval_kernel(
     const int* __restrict__ keys, const u32* __restrict__ table,
     u32* __restrict__ out, const u32* __restrict__ aes_tabs,
     uint4* __restrict__ scratch, int depth, int zlog, int slog, int n_units,
-    long long n) {
+    long long n, Bins... bins) {
+  constexpr bool BINNED = sizeof...(Bins) == 1;
+  static_assert(BINNED ? FUSED : sizeof...(Bins) == 0, "bins: one const int*");
   extern __shared__ u32 smem[];
   const EvalGeom g(depth, zlog);
   const int Z = g.Z, DS = g.DS, lds_base = g.lds_base;
@@ -255,6 +269,15 @@ __global__ __launch_bounds__(256 * K) void dpf_eval_kernel(
     const u32 cwl[2][2] = {{uni(cw_lds[0].x), uni(cw_lds[1].x)},
                            {uni(cw_lds[kCwPerSel].x),
                             uni(cw_lds[kCwPerSel + 1].x)}};
+
+    // The unit's bin block.  key_id is the same for the whole unit, hence
+    // for the wave (Z % 64 == 0), which the compiler cannot see for K > 1.
+    // Surplus units never get here, so they never read bins.
+    if constexpr (BINNED) {
+      const u32 bin = __builtin_amdgcn_readfirstlane(
+          (u32)bin_ids(bins...)[key_id]);
+      table += (unsigned long long)bin * (unsigned long long)n * 16ull;
+    }
 
     for (long long j = j_lo; j < j_hi; ++j) {
       // Issue the two table-row loads first: the leaf ciphers below hide
@@ -403,21 +426,22 @@ int eval_units_per_wg(int prf, int n_units) {
 
 namespace {
 
-template <int PRF, bool FUSED>
+// bins: nothing, or the binned kernel's device id array
+template <int PRF, bool FUSED, class... Bins>
 void launch_eval_t(const int* keys, const u32* table, u32* out,
                    const u32* aes_tabs, int batch, long long n, int depth,
                    int zlog, hipStream_t stream, uint4* own_scratch,
-                   size_t own_scratch_bytes) {
+                   size_t own_scratch_bytes, Bins... bins) {
   const EvalGeom g(depth, zlog);
   const int slog = slog_for(batch, g.DS);
   const int n_units = batch << slog;
   const int K = eval_units_per_wg(PRF, n_units);
   const size_t shmem = g.lds_bytes(PRF, K);
-  auto kern = dpf_eval_kernel<PRF, FUSED, 1>;
+  auto kern = dpf_eval_kernel<PRF, FUSED, 1, Bins...>;
   if constexpr (PRF == PRF_AES128) {
-    if (K == 2) kern = dpf_eval_kernel<PRF, FUSED, 2>;
-    if (K == 3) kern = dpf_eval_kernel<PRF, FUSED, 3>;
-    if (K == 4) kern = dpf_eval_kernel<PRF, FUSED, 4>;
+    if (K == 2) kern = dpf_eval_kernel<PRF, FUSED, 2, Bins...>;
+    if (K == 3) kern = dpf_eval_kernel<PRF, FUSED, 3, Bins...>;
+    if (K == 4) kern = dpf_eval_kernel<PRF, FUSED, 4, Bins...>;
   }
   if (shmem >= 65536) allow_large_lds((const void*)kern);
   // Caller-owned scratch (launches that may overlap on different streams
@@ -436,16 +460,17 @@ void launch_eval_t(const int* keys, const u32* table, u32* out,
   }
   hipLaunchKernelGGL(kern, dim3((unsigned)((n_units + K - 1) / K)),
                      dim3((unsigned)(K * g.Z)), shmem, stream, keys, table,
-                     out, aes_tabs, scratch, depth, zlog, slog, n_units, n);
+                     out, aes_tabs, scratch, depth, zlog, slog, n_units, n,
+                     bins...);
   HIP_CHECK(hipGetLastError());
 }
 
-template <bool FUSED>
+template <bool FUSED, class... Bins>
 void launch_eval_dispatch(std::uintptr_t keys, std::uintptr_t table,
                           std::uintptr_t out, std::uintptr_t aes_tabs,
                           int batch, long long n, int depth, int zlog, int prf,
                           std::uintptr_t stream, std::uintptr_t scratch,
-                          std::size_t scratch_bytes) {
+                          std::size_t scratch_bytes, Bins... bins) {
   if (batch <= 0) return;
   if (depth < 1 || ((long long)1 << depth) != n)
     throw std::invalid_argument("bad depth/n");
@@ -459,7 +484,8 @@ void launch_eval_dispatch(std::uintptr_t keys, std::uintptr_t table,
   auto* sc = reinterpret_cast<uint4*>(scratch);
   with_prf(prf, [&](auto P) {
     launch_eval_t<decltype(P)::value, FUSED>(k, tb, o, a, batch, n, depth,
-                                             zlog, s, sc, scratch_bytes);
+                                             zlog, s, sc, scratch_bytes,
+                                             bins...);
   });
 }
 
@@ -471,6 +497,23 @@ void launch_fused(std::uintptr_t keys, std::uintptr_t table, std::uintptr_t out,
                   std::uintptr_t scratch, std::size_t scratch_bytes) {
   launch_eval_dispatch<true>(keys, table, out, aes_tabs, batch, n, depth, zlog,
                              prf, stream, scratch, scratch_bytes);
+}
+
+void launch_fused_binned(std::uintptr_t keys, std::uintptr_t table,
+                         std::uintptr_t bins, std::uintptr_t out,
+                         std::uintptr_t aes_tabs, int batch, long long n,
+                         int depth, int zlog, long long num_bins, int prf,
+                         std::uintptr_t stream, std::uintptr_t scratch,
+                         std::size_t scratch_bytes) {
+  if (num_bins < 1) throw std::invalid_argument("num_bins must be >= 1");
+  // the whole table (num_bins * n rows of 64 bytes) must be addressable
+  if (n > 0 && num_bins > (long long)(SIZE_MAX / 64) / n)
+    throw std::invalid_argument("num_bins * n * 64 bytes overflows");
+  if (batch > 0 && bins == 0)
+    throw std::invalid_argument("bins must be a device pointer");
+  launch_eval_dispatch<true>(keys, table, out, aes_tabs, batch, n, depth, zlog,
+                             prf, stream, scratch, scratch_bytes,
+                             reinterpret_cast<const int*>(bins));
 }
 
 int eval_slog(int batch, int depth, int zlog) {

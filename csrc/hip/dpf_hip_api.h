@@ -24,6 +24,21 @@ void launch_fused(std::uintptr_t keys, std::uintptr_t table, std::uintptr_t out,
                   std::uintptr_t scratch = 0, std::size_t scratch_bytes = 0);
 std::size_t eval_scratch_bytes(int batch, int depth, int zlog);
 
+// Binned variant of launch_fused (batch PIR): key i is evaluated against its
+// own bin in one launch.
+//   table: device ptr, u32 [num_bins][n][16]; every block of n = 1 << depth
+//          rows is in leaf_perm(n, zlog) order
+//   bins:  device ptr, int32 [batch]; key i reads block bins[i].  The ids
+//          live on the device, so the launcher cannot check them: the caller
+//          guarantees 0 <= bins[i] < num_bins
+// Geometry, scratch and output are those of launch_fused for one bin.
+void launch_fused_binned(std::uintptr_t keys, std::uintptr_t table,
+                         std::uintptr_t bins, std::uintptr_t out,
+                         std::uintptr_t aes_tabs, int batch, long long n,
+                         int depth, int zlog, long long num_bins, int prf,
+                         std::uintptr_t stream, std::uintptr_t scratch = 0,
+                         std::size_t scratch_bytes = 0);
+
 // Launch geometry of launch_fused / launch_expand, for tests that assert
 // the regime they hit.  eval_slog: log2 of the per-key segment split
 // (j-split); pure host arithmetic, no HIP call.  eval_units_per_wg: the

@@ -16,6 +16,7 @@ Public API parity (reference dpf.py:35-137):
 
 try:
     from gpudpf.dpf import DPF  # noqa: F401
+    from gpudpf.binned import BinnedDPF  # noqa: F401
     from gpudpf.dist import ReplicatedDPF, ShardedDPF  # noqa: F401
     from gpudpf.serving import GraphedServer  # noqa: F401
 except ImportError:
@@ -23,5 +24,6 @@ except ImportError:
     # the bare package must still work so `gpudpf._build` can bootstrap
     # (`python -m gpudpf._build` or __graft_entry__.build()).
     DPF = None  # type: ignore[assignment]
+    BinnedDPF = None  # type: ignore[assignment]
 
 __version__ = "0.1.0"
