@@ -60,9 +60,9 @@ GrowScratch g_eval_scratch;
 
 // DFS sibling-stack levels kept in LDS (deeper levels: registers;
 // shallower: global scratch)
-#define MAX_LDS_LEVELS 4
+constexpr int MAX_LDS_LEVELS = 4;
 // Most (key, segment) units one AES workgroup walks (they share the table)
-#define AES_MAX_UNITS 4
+constexpr int AES_MAX_UNITS = 4;
 
 // Geometry of one eval launch, the single statement of where every
 // sibling-stack level lives and how large the LDS and scratch slices are.
@@ -95,13 +95,10 @@ struct EvalGeom {
         shared_u4(Z * (lds_levels > 2 ? lds_levels : 2)),
         unit_u32((2 * kCwPerSel + shared_u4) * 4 + (Z >> 6) * 16) {}
 
-  // u32s of LDS in front of the unit slices (the replicated AES table)
-  static __host__ __device__ constexpr int table_u32(int prf) {
-    return prf == PRF_AES128 ? AES_LDS_WORDS : 0;
-  }
-  // Dynamic LDS bytes of a workgroup of K units
+  // Dynamic LDS bytes of a workgroup of K units: the replicated AES table
+  // in front of the unit slices
   std::size_t lds_bytes(int prf, int K) const {
-    return ((std::size_t)table_u32(prf) + (std::size_t)K * unit_u32) * 4;
+    return ((std::size_t)aes_lds_u32(prf) + (std::size_t)K * unit_u32) * 4;
   }
   // uint4s of global sibling-stack scratch in front of unit `unit`'s rows:
   // one Z-wide row per unit and global level (units index it, so it does
@@ -193,7 +190,7 @@ __global__ __launch_bounds__(256 * K) void dpf_eval_kernel(
   const int seg = unit & ((1 << slog) - 1);
   const long long key_base = (long long)key_id * kKeyInts;
 
-  u32* unit_lds = smem + EvalGeom::table_u32(PRF) + u_local * g.unit_u32;
+  u32* unit_lds = smem + aes_lds_u32(PRF) + u_local * g.unit_u32;
   uint4* cw_lds = reinterpret_cast<uint4*>(unit_lds);  // 2 * kCwPerSel entries
   uint4* shared_region = cw_lds + 2 * kCwPerSel;
   u32* red = reinterpret_cast<u32*>(shared_region + g.shared_u4);
@@ -205,13 +202,10 @@ __global__ __launch_bounds__(256 * K) void dpf_eval_kernel(
       cw_lds[idx] =
           reinterpret_cast<const uint4*>(keys + key_base + kKeyCwInt)[idx];
   }
-  if constexpr (PRF == PRF_AES128) aes_stage_table(smem, aes_tabs);
-  AesLds T{((u32)threadIdx.x & 63u) << 2};
+  aes_stage_table<PRF>(smem, aes_tabs);
+  const AesLds T = AesLds::lane();
   uint4* pp = shared_region;
-  if (active && t == 0) {
-    const int* rp = keys + key_base + kKeyRootInt;
-    pp[0] = make_uint4((u32)rp[0], (u32)rp[1], (u32)rp[2], (u32)rp[3]);
-  }
+  if (active && t == 0) pp[0] = key_root(keys + key_base);
   __syncthreads();
 
   // Phase 1: root -> Z frontier seeds (frontier position t has the
@@ -443,7 +437,7 @@ void launch_eval_t(const int* keys, const u32* table, u32* out,
     if (K == 3) kern = dpf_eval_kernel<PRF, FUSED, 3, Bins...>;
     if (K == 4) kern = dpf_eval_kernel<PRF, FUSED, 4, Bins...>;
   }
-  if (shmem >= 65536) allow_large_lds((const void*)kern);
+  allow_large_lds((const void*)kern, shmem);
   // Caller-owned scratch (launches that may overlap on different streams
   // each bring their own: units with equal index in two kernels in flight
   // would overwrite each other's sibling stacks) or the shared per-device
@@ -472,20 +466,14 @@ void launch_eval_dispatch(std::uintptr_t keys, std::uintptr_t table,
                           std::uintptr_t stream, std::uintptr_t scratch,
                           std::size_t scratch_bytes, Bins... bins) {
   if (batch <= 0) return;
-  if (depth < 1 || ((long long)1 << depth) != n)
-    throw std::invalid_argument("bad depth/n");
+  check_domain(depth, n);
   if (zlog < 6 || zlog >= depth)
     throw std::invalid_argument("zlog must be in [6, depth)");
-  auto* k = reinterpret_cast<const int*>(keys);
-  auto* tb = reinterpret_cast<const u32*>(table);
-  auto* o = reinterpret_cast<u32*>(out);
-  auto* a = reinterpret_cast<const u32*>(aes_tabs);
-  auto s = reinterpret_cast<hipStream_t>(stream);
-  auto* sc = reinterpret_cast<uint4*>(scratch);
   with_prf(prf, [&](auto P) {
-    launch_eval_t<decltype(P)::value, FUSED>(k, tb, o, a, batch, n, depth,
-                                             zlog, s, sc, scratch_bytes,
-                                             bins...);
+    launch_eval_t<decltype(P)::value, FUSED>(
+        as_ptr<const int>(keys), as_ptr<const u32>(table), as_ptr<u32>(out),
+        as_ptr<const u32>(aes_tabs), batch, n, depth, zlog, as_stream(stream),
+        as_ptr<uint4>(scratch), scratch_bytes, bins...);
   });
 }
 
@@ -513,7 +501,7 @@ void launch_fused_binned(std::uintptr_t keys, std::uintptr_t table,
     throw std::invalid_argument("bins must be a device pointer");
   launch_eval_dispatch<true>(keys, table, out, aes_tabs, batch, n, depth, zlog,
                              prf, stream, scratch, scratch_bytes,
-                             reinterpret_cast<const int*>(bins));
+                             as_ptr<const int>(bins));
 }
 
 int eval_slog(int batch, int depth, int zlog) {

@@ -19,11 +19,7 @@ template <int PRF>
 __global__ __launch_bounds__(PRF == PRF_AES128 ? 1024 : 256) void prf_sol_kernel(
     const u32* __restrict__ aes_tabs, u32* __restrict__ out, int iters) {
   extern __shared__ u32 smem[];
-  if constexpr (PRF == PRF_AES128) {
-    aes_stage_table(smem, aes_tabs);  // table first: LDS byte 0
-    __syncthreads();
-  }
-  AesLds T{((u32)threadIdx.x & 63u) << 2};
+  const AesLds T = aes_lds_init<PRF>(smem, aes_tabs);
   uint4 seed = make_uint4(threadIdx.x + 1, blockIdx.x + 2, 3, 4);
   for (int i = 0; i < iters; ++i) {
     uint4 r0, r1;
@@ -35,18 +31,16 @@ __global__ __launch_bounds__(PRF == PRF_AES128 ? 1024 : 256) void prf_sol_kernel
 
 void launch_prf_sol(std::uintptr_t aes_tabs, std::uintptr_t out, int blocks,
                     int iters, int prf, std::uintptr_t stream) {
-  auto* a = reinterpret_cast<const u32*>(aes_tabs);
-  auto* o = reinterpret_cast<u32*>(out);
-  auto st = reinterpret_cast<hipStream_t>(stream);
-  const size_t shmem = (prf == PRF_AES128) ? AES_LDS_WORDS * 4 : 0;
+  const size_t shmem = aes_lds_u32(prf) * sizeof(u32);
   with_prf(prf, [&](auto P) {
     constexpr int PRF = decltype(P)::value;
-    if (PRF == PRF_AES128) allow_large_lds((const void*)prf_sol_kernel<PRF>);
+    allow_large_lds((const void*)prf_sol_kernel<PRF>, shmem);
     // AES: same thread count in workgroups of 1024 where it divides: like
     // the eval kernel's K = 4, four times the waves share one 64 KiB table.
     const bool wide = PRF == PRF_AES128 && blocks % 4 == 0;
     hipLaunchKernelGGL(prf_sol_kernel<PRF>, dim3(wide ? blocks / 4 : blocks),
-                       dim3(wide ? 1024 : 256), shmem, st, a, o, iters);
+                       dim3(wide ? 1024 : 256), shmem, as_stream(stream),
+                       as_ptr<const u32>(aes_tabs), as_ptr<u32>(out), iters);
   });
   HIP_CHECK(hipGetLastError());
 }
@@ -84,11 +78,7 @@ __global__ __launch_bounds__(256) void probe_prf_kernel(
     uint4* __restrict__ single0, uint4* __restrict__ single1,
     u32* __restrict__ low0, u32* __restrict__ low1, int count) {
   extern __shared__ u32 smem[];
-  if constexpr (PRF == PRF_AES128) {
-    aes_stage_table(smem, aes_tabs);  // table first: LDS byte 0
-    __syncthreads();
-  }
-  AesLds T{((u32)threadIdx.x & 63u) << 2};
+  const AesLds T = aes_lds_init<PRF>(smem, aes_tabs);
   const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
   if (i >= count) return;
   const uint4 s = seeds[i];
@@ -107,13 +97,11 @@ __global__ __launch_bounds__(256) void probe_prf_kernel(
 void launch_probe_alu(std::uintptr_t a, std::uintptr_t b,
                       std::uintptr_t add_out, std::uintptr_t mul_out,
                       int count, std::uintptr_t stream) {
-  auto st = reinterpret_cast<hipStream_t>(stream);
   const int blocks = (count + 255) / 256;
-  hipLaunchKernelGGL(probe_alu_kernel, dim3(blocks), dim3(256), 0, st,
-                     reinterpret_cast<const uint4*>(a),
-                     reinterpret_cast<const uint4*>(b),
-                     reinterpret_cast<uint4*>(add_out),
-                     reinterpret_cast<uint4*>(mul_out), count);
+  hipLaunchKernelGGL(probe_alu_kernel, dim3(blocks), dim3(256), 0,
+                     as_stream(stream), as_ptr<const uint4>(a),
+                     as_ptr<const uint4>(b), as_ptr<uint4>(add_out),
+                     as_ptr<uint4>(mul_out), count);
   HIP_CHECK(hipGetLastError());
 }
 
@@ -122,22 +110,17 @@ void launch_probe_prf(std::uintptr_t seeds, std::uintptr_t aes_tabs,
                       std::uintptr_t single0, std::uintptr_t single1,
                       std::uintptr_t low0, std::uintptr_t low1, int count,
                       int prf, std::uintptr_t stream) {
-  auto st = reinterpret_cast<hipStream_t>(stream);
   const int blocks = (count + 255) / 256;
-  const size_t shmem = (prf == PRF_AES128) ? AES_LDS_WORDS * 4 : 0;
-  auto* sp = reinterpret_cast<const uint4*>(seeds);
-  auto* ap = reinterpret_cast<const u32*>(aes_tabs);
-  auto* p0 = reinterpret_cast<uint4*>(pair0);
-  auto* p1 = reinterpret_cast<uint4*>(pair1);
-  auto* s0 = reinterpret_cast<uint4*>(single0);
-  auto* s1 = reinterpret_cast<uint4*>(single1);
-  auto* l0 = reinterpret_cast<u32*>(low0);
-  auto* l1 = reinterpret_cast<u32*>(low1);
+  const size_t shmem = aes_lds_u32(prf) * sizeof(u32);
   with_prf(prf, [&](auto P) {
     constexpr int PRF = decltype(P)::value;
-    if (PRF == PRF_AES128) allow_large_lds((const void*)probe_prf_kernel<PRF>);
+    allow_large_lds((const void*)probe_prf_kernel<PRF>, shmem);
     hipLaunchKernelGGL(probe_prf_kernel<PRF>, dim3(blocks), dim3(256), shmem,
-                       st, sp, ap, p0, p1, s0, s1, l0, l1, count);
+                       as_stream(stream), as_ptr<const uint4>(seeds),
+                       as_ptr<const u32>(aes_tabs), as_ptr<uint4>(pair0),
+                       as_ptr<uint4>(pair1), as_ptr<uint4>(single0),
+                       as_ptr<uint4>(single1), as_ptr<u32>(low0),
+                       as_ptr<u32>(low1), count);
   });
   HIP_CHECK(hipGetLastError());
 }

@@ -98,10 +98,9 @@ __global__ __launch_bounds__(256) void dpf_naive_kernel(
   }
   __syncthreads();
 
-  const int* rp = keys + key_base + kKeyRootInt;
   const long long leaf = (long long)blockIdx.y * blockDim.x + t;
   if (leaf >= n) return;
-  uint4 key = make_uint4((u32)rp[0], (u32)rp[1], (u32)rp[2], (u32)rp[3]);
+  uint4 key = key_root(keys + key_base);
   long long rem = leaf;
   for (int i = depth - 1; i >= 0; --i) {
     const u32 bit = (u32)(rem & 1);
@@ -133,12 +132,12 @@ __global__ __launch_bounds__(256) void dpf_bfs_level_kernel(
     uint4* __restrict__ children, u32* __restrict__ out,
     const u32* __restrict__ aes_tabs, int level, int depth, long long n) {
   extern __shared__ u32 smem[];
-  uint4* cw_lvl = reinterpret_cast<uint4*>(
-      smem + (PRF == PRF_AES128 ? AES_LDS_WORDS : 0));  // table first
+  uint4* cw_lvl =
+      reinterpret_cast<uint4*>(smem + aes_lds_u32(PRF));  // table first
   const int t = (int)threadIdx.x;
   const int key_id = (int)blockIdx.y;
   const long long key_base = (long long)key_id * kKeyInts;
-  if constexpr (PRF == PRF_AES128) aes_stage_table(smem, aes_tabs);
+  aes_stage_table<PRF>(smem, aes_tabs);
   // stage this level's 4 correction words (cw[sel][2i+b], i = eval level)
   const int i_eval = depth - 1 - level;
   if (t < 4) {
@@ -147,7 +146,7 @@ __global__ __launch_bounds__(256) void dpf_bfs_level_kernel(
         [sel * kCwPerSel + i_eval * 2 + b];
   }
   __syncthreads();
-  AesLds T{((u32)t & 63u) << 2};
+  const AesLds T = AesLds::lane();
 
   const long long n_parents = (long long)1 << level;
   const long long p = (long long)blockIdx.x * blockDim.x + t;
@@ -155,8 +154,7 @@ __global__ __launch_bounds__(256) void dpf_bfs_level_kernel(
 
   uint4 seed;
   if (level == 0) {
-    const int* rp = keys + key_base + kKeyRootInt;
-    seed = make_uint4((u32)rp[0], (u32)rp[1], (u32)rp[2], (u32)rp[3]);
+    seed = key_root(keys + key_base);
   } else {
     seed = parents[(u64)key_id * (n_parents) + (u64)p];
     // parents buffer is sized per level: indexed [key][p] with stride
@@ -200,11 +198,7 @@ __global__ __launch_bounds__(256) void dpf_coop_kernel(
     long long n) {
   extern __shared__ u32 smem[];
   const int t = (int)threadIdx.x;
-  if constexpr (PRF == PRF_AES128) {
-    aes_stage_table(smem, aes_tabs);  // table first: LDS byte 0
-    __syncthreads();
-  }
-  AesLds T{((u32)t & 63u) << 2};
+  const AesLds T = aes_lds_init<PRF>(smem, aes_tabs);
   auto grid = cooperative_groups::this_grid();
   const long long gsize = (long long)gridDim.x * blockDim.x;
   const long long gtid = (long long)blockIdx.x * blockDim.x + t;
@@ -220,8 +214,7 @@ __global__ __launch_bounds__(256) void dpf_coop_kernel(
     for (long long p = gtid; p < n_parents; p += gsize) {
       uint4 seed;
       if (level == 0) {
-        const int* rp = keys + kKeyRootInt;
-        seed = make_uint4((u32)rp[0], (u32)rp[1], (u32)rp[2], (u32)rp[3]);
+        seed = key_root(keys);
       } else {
         seed = ping[p];
       }
@@ -280,8 +273,8 @@ void launch_coop_t(const int* keys, const u32* table, u32* out,
                    const u32* aes_tabs, uint4* ping, uint4* pong, int depth,
                    int zlog, long long n, hipStream_t st) {
   auto kern = dpf_coop_kernel<PRF, FUSED>;
-  const size_t shmem = (PRF == PRF_AES128) ? AES_LDS_WORDS * 4 : 0;
-  if (PRF == PRF_AES128) allow_large_lds((const void*)kern);
+  const size_t shmem = aes_lds_u32(PRF) * sizeof(u32);
+  allow_large_lds((const void*)kern, shmem);
   int dev = 0;
   HIP_CHECK(hipGetDevice(&dev));
   int coop = 0;
@@ -311,21 +304,17 @@ void launch_coop_t(const int* keys, const u32* table, u32* out,
 void launch_coop(std::uintptr_t keys, std::uintptr_t table, std::uintptr_t out,
                  std::uintptr_t aes_tabs, long long n, int depth, int zlog,
                  int prf, bool fused, std::uintptr_t stream) {
-  if (depth < 1 || ((long long)1 << depth) != n)
-    throw std::invalid_argument("bad depth/n");
-  auto st = reinterpret_cast<hipStream_t>(stream);
+  check_domain(depth, n);
   const size_t half = (size_t)(n / 2) * sizeof(uint4);
   uint4* ping =
       static_cast<uint4*>(g_eval_scratch.get(2 * half > 0 ? 2 * half : 32));
   uint4* pong = ping + (size_t)(n / 2);
-  auto* kp = reinterpret_cast<const int*>(keys);
-  auto* tp = reinterpret_cast<const u32*>(table);
-  auto* op = reinterpret_cast<u32*>(out);
-  auto* ap = reinterpret_cast<const u32*>(aes_tabs);
   with_prf(prf, [&](auto P) {
     constexpr int PRF = decltype(P)::value;
     auto launch = fused ? launch_coop_t<PRF, true> : launch_coop_t<PRF, false>;
-    launch(kp, tp, op, ap, ping, pong, depth, zlog, n, st);
+    launch(as_ptr<const int>(keys), as_ptr<const u32>(table), as_ptr<u32>(out),
+           as_ptr<const u32>(aes_tabs), ping, pong, depth, zlog, n,
+           as_stream(stream));
   });
 }
 
@@ -334,10 +323,8 @@ template <int PRF>
 void launch_bfs_t(const int* keys, u32* out, const u32* aes_tabs,
                   uint4* ping, uint4* pong, int batch, long long n, int depth,
                   hipStream_t st) {
-  const size_t shmem =
-      (PRF == PRF_AES128 ? AES_LDS_WORDS * 4 : 0) + 4 * sizeof(uint4);
-  if (PRF == PRF_AES128)
-    allow_large_lds((const void*)dpf_bfs_level_kernel<PRF>);
+  const size_t shmem = aes_lds_u32(PRF) * sizeof(u32) + 4 * sizeof(uint4);
+  allow_large_lds((const void*)dpf_bfs_level_kernel<PRF>, shmem);
   for (int level = 0; level < depth; ++level) {
     const long long n_parents = (long long)1 << level;
     const long long blocks = (n_parents + 255) / 256;
@@ -356,9 +343,7 @@ void launch_bfs(std::uintptr_t keys, std::uintptr_t out,
                 std::uintptr_t aes_tabs, int batch, long long n, int depth,
                 int prf, std::uintptr_t stream) {
   if (batch <= 0) return;
-  if (depth < 1 || ((long long)1 << depth) != n)
-    throw std::invalid_argument("bad depth/n");
-  auto st = reinterpret_cast<hipStream_t>(stream);
+  check_domain(depth, n);
   // two ping-pong frontier buffers, each batch * n/2 seeds
   const size_t half = (size_t)batch * (size_t)(n / 2) * sizeof(uint4);
   if (2 * half > (size_t)48 << 30)
@@ -366,12 +351,10 @@ void launch_bfs(std::uintptr_t keys, std::uintptr_t out,
   uint4* ping =
       static_cast<uint4*>(g_eval_scratch.get(2 * half > 0 ? 2 * half : 16));
   uint4* pong = ping + (size_t)batch * (size_t)(n / 2);
-  auto* kp = reinterpret_cast<const int*>(keys);
-  auto* op = reinterpret_cast<u32*>(out);
-  auto* ap = reinterpret_cast<const u32*>(aes_tabs);
   with_prf(prf, [&](auto P) {
-    launch_bfs_t<decltype(P)::value>(kp, op, ap, ping, pong, batch, n, depth,
-                                     st);
+    launch_bfs_t<decltype(P)::value>(
+        as_ptr<const int>(keys), as_ptr<u32>(out), as_ptr<const u32>(aes_tabs),
+        ping, pong, batch, n, depth, as_stream(stream));
   });
 }
 
@@ -379,19 +362,18 @@ void launch_naive(std::uintptr_t keys, std::uintptr_t out,
                   std::uintptr_t aes_tabs, int batch, long long n, int depth,
                   int prf, std::uintptr_t stream) {
   if (batch <= 0) return;
+  check_domain(depth, n);
   const int threads = 256;
   dim3 grid((unsigned)batch, (unsigned)((n + threads - 1) / threads));
   const size_t shmem =
       2 * kCwPerSel * 16 + (prf == PRF_AES128 ? 1280 * 4 : 0);
-  auto* k = reinterpret_cast<const int*>(keys);
-  auto* o = reinterpret_cast<u32*>(out);
-  auto* a = reinterpret_cast<const u32*>(aes_tabs);
-  auto s = reinterpret_cast<hipStream_t>(stream);
   with_prf(prf, [&](auto P) {
     hipLaunchKernelGGL(dpf_naive_kernel<decltype(P)::value>, grid,
-                       dim3(threads), shmem, s, k, o, a, depth, n);
+                       dim3(threads), shmem, as_stream(stream),
+                       as_ptr<const int>(keys), as_ptr<u32>(out),
+                       as_ptr<const u32>(aes_tabs), depth, n);
+    HIP_CHECK(hipGetLastError());
   });
-  HIP_CHECK(hipGetLastError());
 }
 
 }  // namespace gpudpf_hip

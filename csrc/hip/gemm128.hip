@@ -26,8 +26,6 @@ namespace gpudpf_hip {
 
 namespace {
 
-using u32 = std::uint32_t;
-using u64 = std::uint64_t;
 using u128 = unsigned __int128;
 
 struct u128v {
@@ -111,17 +109,16 @@ void launch_gemm128(std::uintptr_t a, std::uintptr_t bt, std::uintptr_t c,
   long long kchunk = ((K + ksplit - 1) / ksplit + TK - 1) / TK * TK;
   dim3 grid((unsigned)((M + 15) / 16), (unsigned)((N + 15) / 16),
             (unsigned)ksplit);
-  auto s = reinterpret_cast<hipStream_t>(stream);
+  auto s = as_stream(stream);
   hipLaunchKernelGGL(gemm128_kernel, grid, dim3(256), 0, s,
-                     reinterpret_cast<const u128v*>(a),
-                     reinterpret_cast<const u128v*>(bt),
-                     reinterpret_cast<u128v*>(partials), M, N, K, kchunk);
+                     as_ptr<const u128v>(a), as_ptr<const u128v>(bt),
+                     as_ptr<u128v>(partials), M, N, K, kchunk);
   HIP_CHECK(hipGetLastError());
   const long long MN = M * N;
   hipLaunchKernelGGL(gemm128_reduce_kernel,
                      dim3((unsigned)((MN + 255) / 256)), dim3(256), 0, s,
-                     reinterpret_cast<const u128v*>(partials),
-                     reinterpret_cast<u128v*>(c), MN, ksplit);
+                     as_ptr<const u128v>(partials), as_ptr<u128v>(c), MN,
+                     ksplit);
   HIP_CHECK(hipGetLastError());
 }
 

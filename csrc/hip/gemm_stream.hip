@@ -47,9 +47,6 @@
 
 namespace gpudpf_hip {
 
-using u32 = std::uint32_t;
-using u64 = std::uint64_t;
-
 namespace {
 
 constexpr int kThreads = 64;       // one wave per workgroup
@@ -241,10 +238,10 @@ void launch_gemm_u32_stream(std::uintptr_t a, std::uintptr_t b,
   if (batch < 1 || batch > kMaxB)
     throw std::invalid_argument("stream GEMM batch must be 1..16 "
                                 "(python wrapper chunks larger batches)");
-  auto* ap = reinterpret_cast<const u32*>(a);
-  auto* bp = reinterpret_cast<const u32*>(b);
-  auto* cp = reinterpret_cast<u32*>(c);
-  auto st = reinterpret_cast<hipStream_t>(stream);
+  auto* ap = as_ptr<const u32>(a);
+  auto* bp = as_ptr<const u32>(b);
+  auto* cp = as_ptr<u32>(c);
+  auto st = as_stream(stream);
   if (batch <= 4) launch_b<4>(ap, bp, cp, batch, K, N, st);
   else if (batch <= 8) launch_b<8>(ap, bp, cp, batch, K, N, st);
   else launch_b<16>(ap, bp, cp, batch, K, N, st);

@@ -31,7 +31,6 @@ namespace gpudpf_hip {
 
 namespace {
 
-using u32 = std::uint32_t;
 using s8 = signed char;
 typedef int v4i __attribute__((ext_vector_type(4)));
 
@@ -117,12 +116,11 @@ __global__ __launch_bounds__(256) void gemm_u32_mfma_kernel(
 
 void launch_digits(std::uintptr_t in, std::uintptr_t out, long long count,
                    std::uintptr_t stream) {
-  auto s = reinterpret_cast<hipStream_t>(stream);
   long long blocks = (count + 255) / 256;
   if (blocks > (1 << 20)) blocks = 1 << 20;  // grid-stride beyond this
-  hipLaunchKernelGGL(digits_kernel, dim3((unsigned)blocks), dim3(256), 0, s,
-                     reinterpret_cast<const u32*>(in),
-                     reinterpret_cast<s8*>(out), count, count);
+  hipLaunchKernelGGL(digits_kernel, dim3((unsigned)blocks), dim3(256), 0,
+                     as_stream(stream), as_ptr<const u32>(in),
+                     as_ptr<s8>(out), count, count);
   HIP_CHECK(hipGetLastError());
 }
 
@@ -149,13 +147,11 @@ void launch_gemm_u32_mfma(std::uintptr_t da, std::uintptr_t dbt,
                           long long K, std::uintptr_t stream) {
   const auto split = gemm_u32_split(M, N, K);
   const long long ks = split.first, kchunk = split.second;
-  auto s = reinterpret_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(gemm_u32_mfma_kernel,
                      dim3((unsigned)(M / 64), (unsigned)(N / 16),
                           (unsigned)ks),
-                     dim3(256), 0, s, reinterpret_cast<const s8*>(da),
-                     reinterpret_cast<const s8*>(dbt),
-                     reinterpret_cast<u32*>(c), M, N, K, kchunk);
+                     dim3(256), 0, as_stream(stream), as_ptr<const s8>(da),
+                     as_ptr<const s8>(dbt), as_ptr<u32>(c), M, N, K, kchunk);
   HIP_CHECK(hipGetLastError());
 }
 

@@ -1,10 +1,12 @@
 // Host-side helpers shared by the HIP translation units of gpudpf._hip:
-// error checking, the large-LDS opt-in, runtime -> compile-time PRF dispatch
+// error checking, typed views of the launchers' integer arguments, the
+// domain check, the large-LDS opt-in, runtime -> compile-time PRF dispatch
 // and the grow-only device scratch.  Internal: not part of dpf_hip_api.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
+#include <cstdint>
 #include <mutex>
 #include <set>
 #include <stdexcept>
@@ -35,11 +37,32 @@ using gpudpf::PRF_CHACHA20;
 using gpudpf::PRF_DUMMY;
 using gpudpf::PRF_SALSA20;
 
+using u32 = std::uint32_t;
+using u64 = std::uint64_t;
+
+// Device pointers and streams cross dpf_hip_api.h as integers: typed views.
+template <class T>
+T* as_ptr(std::uintptr_t p) {
+  return reinterpret_cast<T*>(p);
+}
+inline hipStream_t as_stream(std::uintptr_t s) {
+  return reinterpret_cast<hipStream_t>(s);
+}
+
+// The domain is n = 2^depth leaves, depth >= 1 (a key stages 64 levels of
+// correction words; a depth that does not match n would index past them).
+inline void check_domain(int depth, long long n) {
+  if (depth < 1 || ((long long)1 << depth) != n)
+    throw std::invalid_argument("bad depth/n");
+}
+
 // Launches that ask for 64 KiB or more of dynamic LDS (every kernel that
-// holds the replicated AES table) must raise the kernel's limit first.
-// Done once per (kernel, device), so a launch replayed or captured later
-// makes no runtime call beyond the launch itself.
-inline void allow_large_lds(const void* kern) {
+// holds the replicated AES table) must raise the kernel's limit first;
+// smaller launches need nothing.  Done once per (kernel, device), so a
+// launch replayed or captured later makes no runtime call beyond the
+// launch itself.
+inline void allow_large_lds(const void* kern, std::size_t lds_bytes) {
+  if (lds_bytes < 65536) return;
   static std::mutex mu;
   static std::set<std::pair<const void*, int>> done;
   int dev = 0;

@@ -6,13 +6,13 @@
 // CONTRACT for kernels that build an AesLds (see the AES section below):
 // no static LDS, and the replicated te0 table (aes_stage_table) first in
 // the dynamic LDS map, so that the table starts at LDS byte 0.
+//
+// How the file is organised, and how a change to it is checked for equal
+// generated code: docs/KERNEL_NOTES.md.
 #pragma once
 #include "hip_util.h"
 
 namespace gpudpf_hip {
-
-using u32 = std::uint32_t;
-using u64 = std::uint64_t;
 
 // ---------------------------------------------------------------------------
 // 128-bit helpers (uint4 limbs, x = bits 31..0 ... w = bits 127..96)
@@ -32,9 +32,12 @@ __device__ __forceinline__ u32 rotr8(u32 v) { return (v >> 8) | (v << 24); }
 __device__ __forceinline__ u32 rotr16(u32 v) { return (v >> 16) | (v << 16); }
 __device__ __forceinline__ u32 rotr24(u32 v) { return (v >> 24) | (v << 8); }
 
-// AES replicated-table geometry
-#define AES_REP 64
-#define AES_LDS_WORDS (256 * AES_REP)  // 64 KiB
+// The unpacked root seed of the key that starts at `key` (wire layout in
+// dpf_core.h)
+__device__ __forceinline__ uint4 key_root(const int* key) {
+  const int* rp = key + kKeyRootInt;
+  return make_uint4((u32)rp[0], (u32)rp[1], (u32)rp[2], (u32)rp[3]);
+}
 
 // ---------------------------------------------------------------------------
 // DUMMY: seed*(pos+4242) + (pos+4242) over Z_2^128
@@ -50,225 +53,183 @@ __device__ __forceinline__ uint4 prf_dummy_full(uint4 seed, u32 pos) {
 }
 
 // ---------------------------------------------------------------------------
-// Salsa20/12 (conventions: seed words 1..4 high->low, pos word 9, output
-// words 1..4 — see csrc/core/prf.cc)
+// Salsa20/12 and ChaCha20/12 over N interleaved chains.  The state is
+// x[word][chain]; chain i is the block at pos + i, so N = 2 from pos 0 is
+// both children in one pass: the two blocks are independent dependency
+// chains, so interleaving doubles the ILP the SIMD can draw on — the DFS
+// runs at ~2 waves/SIMD where a single chain's QR latency is not fully
+// hidden.  Every step of a quarter-round therefore runs over all chains
+// before the next step starts.  The word indices are constants after
+// inlining, so the state lives in registers.
+//
+// PART: a quarter-round runs only its first PART steps.  The LOW drivers
+// (leaf level: only the low output word is needed) use it to prune the last
+// double-round to the dataflow cone of that word.
 // ---------------------------------------------------------------------------
-#define SALSA_QR(a, b, c, d)  \
-  b ^= rotl(a + d, 7);        \
-  c ^= rotl(b + a, 9);        \
-  d ^= rotl(c + b, 13);       \
-  a ^= rotl(d + c, 18)
-
-__device__ __forceinline__ uint4 salsa12_core(uint4 seed, u32 pos) {
-  const u32 c0 = 0x65787061u, c5 = 0x6e642033u, c10 = 0x322d6279u,
-            c15 = 0x7465206bu;
-  u32 x0 = c0, x1 = seed.w, x2 = seed.z, x3 = seed.y, x4 = seed.x, x5 = c5,
-      x6 = 0, x7 = 0, x8 = 0, x9 = pos, x10 = c10, x11 = 0, x12 = 0, x13 = 0,
-      x14 = 0, x15 = c15;
+// Every chain starts from the same 16 words; chain i adds i to word `pos_w`.
+template <int N>
+__device__ __forceinline__ void stream_init(u32 (&x)[16][N], int pos_w,
+                                            const u32 (&init)[16]) {
 #pragma unroll
-  for (int r = 0; r < 6; ++r) {
-    SALSA_QR(x0, x4, x8, x12);
-    SALSA_QR(x5, x9, x13, x1);
-    SALSA_QR(x10, x14, x2, x6);
-    SALSA_QR(x15, x3, x7, x11);
-    SALSA_QR(x0, x1, x2, x3);
-    SALSA_QR(x5, x6, x7, x4);
-    SALSA_QR(x10, x11, x8, x9);
-    SALSA_QR(x15, x12, x13, x14);
-  }
-  return make_uint4(x4 + seed.x, x3 + seed.y, x2 + seed.z, x1 + seed.w);
+  for (int w = 0; w < 16; ++w)
+#pragma unroll
+    for (int i = 0; i < N; ++i) x[w][i] = init[w] + (w == pos_w ? i : 0);
 }
 
-// Both children interleaved in one pass: the two blocks (pos=0 / pos=1)
-// are independent dependency chains, so interleaving doubles the ILP the
-// SIMD can draw on — the DFS runs at ~2 waves/SIMD where a single chain's
-// QR latency is not fully hidden.
-#define SALSA_QR2(a, b, c, d, a2, b2, c2, d2) \
-  b ^= rotl(a + d, 7);   b2 ^= rotl(a2 + d2, 7);   \
-  c ^= rotl(b + a, 9);   c2 ^= rotl(b2 + a2, 9);   \
-  d ^= rotl(c + b, 13);  d2 ^= rotl(c2 + b2, 13);  \
-  a ^= rotl(d + c, 18);  a2 ^= rotl(d2 + c2, 18)
+// Chain i's output: the feed-forward of the four words that held the seed,
+// x[lo] (seed.x) down to x[lo - 3] (seed.w).
+template <int N>
+__device__ __forceinline__ uint4 stream_out(const u32 (&x)[16][N], int i,
+                                            int lo, uint4 seed) {
+  return make_uint4(x[lo][i] + seed.x, x[lo - 1][i] + seed.y,
+                    x[lo - 2][i] + seed.z, x[lo - 3][i] + seed.w);
+}
+
+// ---------------------------------------------------------------------------
+// Salsa20/12 (conventions: seed words 1..4 high->low, pos word 9, output
+// words 1..4 — see csrc/core/prf.cc).  QR steps: 1 b, 2 c, 3 d, 4 a.
+// ---------------------------------------------------------------------------
+template <int PART = 4, int N>
+__device__ __forceinline__ void salsa_qr(u32 (&x)[16][N], int a, int b, int c,
+                                         int d) {
+  auto step = [&](int t, int p, int q, int s) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) x[t][i] ^= rotl(x[p][i] + x[q][i], s);
+  };
+  step(b, a, d, 7);
+  if constexpr (PART > 1) step(c, b, a, 9);
+  if constexpr (PART > 2) step(d, c, b, 13);
+  if constexpr (PART > 3) step(a, d, c, 18);
+}
+
+// 12 rounds = 6 double-rounds (column, then row) on chains pos .. pos+N-1.
+// LOW: only the low output word (out[4] = x4 + seed.x) is needed, so the
+// final double-round computes just the dataflow cone of x4:
+// row-QR(x5,x6,x7,x4) needs post-column x5 (full QR), x6 (b,c,d of its QR),
+// x7 (b,c), x4 (b) — 39 ops instead of 96.  Only x[4] is then valid.
+template <bool LOW, int N>
+__device__ __forceinline__ void salsa12(uint4 seed, u32 pos, u32 (&x)[16][N]) {
+  stream_init(x, 9, {0x65787061u, seed.w, seed.z, seed.y, seed.x, 0x6e642033u,
+                     0, 0, 0, pos, 0x322d6279u, 0, 0, 0, 0, 0x7465206bu});
+#pragma unroll
+  for (int r = 0; r < (LOW ? 5 : 6); ++r) {
+    salsa_qr(x, 0, 4, 8, 12);
+    salsa_qr(x, 5, 9, 13, 1);
+    salsa_qr(x, 10, 14, 2, 6);
+    salsa_qr(x, 15, 3, 7, 11);
+    salsa_qr(x, 0, 1, 2, 3);
+    salsa_qr(x, 5, 6, 7, 4);
+    salsa_qr(x, 10, 11, 8, 9);
+    salsa_qr(x, 15, 12, 13, 14);
+  }
+  if constexpr (LOW) {
+    salsa_qr<1>(x, 0, 4, 8, 12);   // new x4 (b)
+    salsa_qr(x, 5, 9, 13, 1);      // new x5 (a: full)
+    salsa_qr<3>(x, 10, 14, 2, 6);  // new x6 (d)
+    salsa_qr<2>(x, 15, 3, 7, 11);  // new x7 (c)
+    salsa_qr<3>(x, 5, 6, 7, 4);    // row: new x4 (d)
+  }
+}
+
+__device__ __forceinline__ uint4 salsa12_core(uint4 seed, u32 pos) {
+  u32 x[16][1];
+  salsa12<false>(seed, pos, x);
+  return stream_out(x, 0, 4, seed);
+}
 
 __device__ __forceinline__ void salsa12_pair_core(uint4 seed, uint4& r0,
                                                   uint4& r1) {
-  const u32 c0 = 0x65787061u, c5 = 0x6e642033u, c10 = 0x322d6279u,
-            c15 = 0x7465206bu;
-  u32 x0 = c0, x1 = seed.w, x2 = seed.z, x3 = seed.y, x4 = seed.x, x5 = c5,
-      x6 = 0, x7 = 0, x8 = 0, x9 = 0, x10 = c10, x11 = 0, x12 = 0, x13 = 0,
-      x14 = 0, x15 = c15;
-  u32 y0 = c0, y1 = x1, y2 = x2, y3 = x3, y4 = x4, y5 = c5, y6 = 0, y7 = 0,
-      y8 = 0, y9 = 1, y10 = c10, y11 = 0, y12 = 0, y13 = 0, y14 = 0, y15 = c15;
-#pragma unroll
-  for (int r = 0; r < 6; ++r) {
-    SALSA_QR2(x0, x4, x8, x12, y0, y4, y8, y12);
-    SALSA_QR2(x5, x9, x13, x1, y5, y9, y13, y1);
-    SALSA_QR2(x10, x14, x2, x6, y10, y14, y2, y6);
-    SALSA_QR2(x15, x3, x7, x11, y15, y3, y7, y11);
-    SALSA_QR2(x0, x1, x2, x3, y0, y1, y2, y3);
-    SALSA_QR2(x5, x6, x7, x4, y5, y6, y7, y4);
-    SALSA_QR2(x10, x11, x8, x9, y10, y11, y8, y9);
-    SALSA_QR2(x15, x12, x13, x14, y15, y12, y13, y14);
-  }
-  r0 = make_uint4(x4 + seed.x, x3 + seed.y, x2 + seed.z, x1 + seed.w);
-  r1 = make_uint4(y4 + seed.x, y3 + seed.y, y2 + seed.z, y1 + seed.w);
+  u32 x[16][2];
+  salsa12<false>(seed, 0, x);
+  r0 = stream_out(x, 0, 4, seed);
+  r1 = stream_out(x, 1, 4, seed);
 }
-
-// Leaf-level variant: only the LOW output word (out[4] = x4 + seed.x) is
-// needed, so the final double-round computes just the dataflow cone of
-// x4: row-QR(x5,x6,x7,x4) needs post-column x5 (full QR), x6 (b,c,d of
-// its QR), x7 (b,c), x4 (b) — 39 ops instead of 96.
-#define SALSA_QR2_HEAD1(a, b, c, d, a2, b2, c2, d2) /* b only */ \
-  b ^= rotl(a + d, 7);   b2 ^= rotl(a2 + d2, 7)
-#define SALSA_QR2_HEAD2(a, b, c, d, a2, b2, c2, d2) /* b, c */ \
-  b ^= rotl(a + d, 7);   b2 ^= rotl(a2 + d2, 7);   \
-  c ^= rotl(b + a, 9);   c2 ^= rotl(b2 + a2, 9)
-#define SALSA_QR2_HEAD3(a, b, c, d, a2, b2, c2, d2) /* b, c, d */ \
-  b ^= rotl(a + d, 7);   b2 ^= rotl(a2 + d2, 7);   \
-  c ^= rotl(b + a, 9);   c2 ^= rotl(b2 + a2, 9);   \
-  d ^= rotl(c + b, 13);  d2 ^= rotl(c2 + b2, 13)
 
 __device__ __forceinline__ void salsa12_pair_low_core(uint4 seed, u32& lo0,
                                                       u32& lo1) {
-  const u32 c0 = 0x65787061u, c5 = 0x6e642033u, c10 = 0x322d6279u,
-            c15 = 0x7465206bu;
-  u32 x0 = c0, x1 = seed.w, x2 = seed.z, x3 = seed.y, x4 = seed.x, x5 = c5,
-      x6 = 0, x7 = 0, x8 = 0, x9 = 0, x10 = c10, x11 = 0, x12 = 0, x13 = 0,
-      x14 = 0, x15 = c15;
-  u32 y0 = c0, y1 = x1, y2 = x2, y3 = x3, y4 = x4, y5 = c5, y6 = 0, y7 = 0,
-      y8 = 0, y9 = 1, y10 = c10, y11 = 0, y12 = 0, y13 = 0, y14 = 0, y15 = c15;
-#pragma unroll
-  for (int r = 0; r < 5; ++r) {
-    SALSA_QR2(x0, x4, x8, x12, y0, y4, y8, y12);
-    SALSA_QR2(x5, x9, x13, x1, y5, y9, y13, y1);
-    SALSA_QR2(x10, x14, x2, x6, y10, y14, y2, y6);
-    SALSA_QR2(x15, x3, x7, x11, y15, y3, y7, y11);
-    SALSA_QR2(x0, x1, x2, x3, y0, y1, y2, y3);
-    SALSA_QR2(x5, x6, x7, x4, y5, y6, y7, y4);
-    SALSA_QR2(x10, x11, x8, x9, y10, y11, y8, y9);
-    SALSA_QR2(x15, x12, x13, x14, y15, y12, y13, y14);
-  }
-  // 6th double-round, pruned to the cone of x4/y4:
-  SALSA_QR2_HEAD1(x0, x4, x8, x12, y0, y4, y8, y12);   // new x4 (b)
-  SALSA_QR2(x5, x9, x13, x1, y5, y9, y13, y1);         // new x5 (a: full)
-  SALSA_QR2_HEAD3(x10, x14, x2, x6, y10, y14, y2, y6); // new x6 (d)
-  SALSA_QR2_HEAD2(x15, x3, x7, x11, y15, y3, y7, y11); // new x7 (c)
-  SALSA_QR2_HEAD3(x5, x6, x7, x4, y5, y6, y7, y4);     // row: new x4 (d)
-  lo0 = x4 + seed.x;
-  lo1 = y4 + seed.x;
+  u32 x[16][2];
+  salsa12<true>(seed, 0, x);
+  lo0 = x[4][0] + seed.x;
+  lo1 = x[4][1] + seed.x;
 }
 
 // ---------------------------------------------------------------------------
-// ChaCha20/12 (seed words 4..7 high->low, pos word 13, output words 4..7)
+// ChaCha20/12 (seed words 4..7 high->low, pos word 13, output words 4..7).
+// QR steps: 1 a+=b, 2 d^=a <<<16, 3 c+=d, 4 b^=c <<<12, 5 a+=b, 6 d^=a <<<8,
+// 7 c+=d, 8 b^=c <<<7.  PART is 6 (d final), 7 (c final) or 8.
 // ---------------------------------------------------------------------------
-#define CHACHA_QR(a, b, c, d) \
-  a += b;  d ^= a;  d = rotl(d, 16); \
-  c += d;  b ^= c;  b = rotl(b, 12); \
-  a += b;  d ^= a;  d = rotl(d, 8);  \
-  c += d;  b ^= c;  b = rotl(b, 7)
+template <int PART = 8, int N>
+__device__ __forceinline__ void chacha_qr(u32 (&x)[16][N], int a, int b, int c,
+                                          int d) {
+  static_assert(PART >= 6 && PART <= 8, "only the tail is ever pruned");
+  auto add = [&](int t, int s) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) x[t][i] += x[s][i];
+  };
+  auto xor_rotl = [&](int t, int s, int r) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) x[t][i] ^= x[s][i];
+#pragma unroll
+    for (int i = 0; i < N; ++i) x[t][i] = rotl(x[t][i], r);
+  };
+  add(a, b);  xor_rotl(d, a, 16);
+  add(c, d);  xor_rotl(b, c, 12);
+  add(a, b);  xor_rotl(d, a, 8);
+  if constexpr (PART > 6) add(c, d);
+  if constexpr (PART > 7) xor_rotl(b, c, 7);
+}
+
+// 12 rounds = 6 double-rounds (column, then diagonal) on chains
+// pos .. pos+N-1.  LOW: only out[7] = x7 + seed.x is needed.  Final
+// double-round cone: diagonal QR(x2,x7,x8,x13) needs its full chain; its
+// inputs need x2 (full col QR), x7 (full: b needs a,c,d), x8 (col QR c
+// through the second c+=d), x13 (col QR d through the second d-rotate) —
+// 56 ops instead of 96.  Only x[7] is then valid.
+template <bool LOW, int N>
+__device__ __forceinline__ void chacha12(uint4 seed, u32 pos,
+                                         u32 (&x)[16][N]) {
+  stream_init(x, 13, {0x65787061u, 0x6e642033u, 0x322d6279u, 0x7465206bu,
+                      seed.w, seed.z, seed.y, seed.x, 0, 0, 0, 0, 0, pos, 0, 0});
+#pragma unroll
+  for (int r = 0; r < (LOW ? 5 : 6); ++r) {
+    chacha_qr(x, 0, 4, 8, 12);
+    chacha_qr(x, 1, 5, 9, 13);
+    chacha_qr(x, 2, 6, 10, 14);
+    chacha_qr(x, 3, 7, 11, 15);
+    chacha_qr(x, 0, 5, 10, 15);
+    chacha_qr(x, 1, 6, 11, 12);
+    chacha_qr(x, 2, 7, 8, 13);
+    chacha_qr(x, 3, 4, 9, 14);
+  }
+  if constexpr (LOW) {
+    chacha_qr<7>(x, 0, 4, 8, 12);  // x8 (c)
+    chacha_qr<6>(x, 1, 5, 9, 13);  // x13 (d)
+    chacha_qr(x, 2, 6, 10, 14);    // x2 (a: full)
+    chacha_qr(x, 3, 7, 11, 15);    // x7 (b: full)
+    chacha_qr(x, 2, 7, 8, 13);     // diagonal: x7 (b)
+  }
+}
 
 __device__ __forceinline__ uint4 chacha12_core(uint4 seed, u32 pos) {
-  u32 x0 = 0x65787061u, x1 = 0x6e642033u, x2 = 0x322d6279u, x3 = 0x7465206bu;
-  u32 x4 = seed.w, x5 = seed.z, x6 = seed.y, x7 = seed.x;
-  u32 x8 = 0, x9 = 0, x10 = 0, x11 = 0, x12 = 0, x13 = pos, x14 = 0, x15 = 0;
-#pragma unroll
-  for (int r = 0; r < 6; ++r) {
-    CHACHA_QR(x0, x4, x8, x12);
-    CHACHA_QR(x1, x5, x9, x13);
-    CHACHA_QR(x2, x6, x10, x14);
-    CHACHA_QR(x3, x7, x11, x15);
-    CHACHA_QR(x0, x5, x10, x15);
-    CHACHA_QR(x1, x6, x11, x12);
-    CHACHA_QR(x2, x7, x8, x13);
-    CHACHA_QR(x3, x4, x9, x14);
-  }
-  return make_uint4(x7 + seed.x, x6 + seed.y, x5 + seed.z, x4 + seed.w);
+  u32 x[16][1];
+  chacha12<false>(seed, pos, x);
+  return stream_out(x, 0, 7, seed);
 }
-
-#define CHACHA_QR2(a, b, c, d, a2, b2, c2, d2)                      \
-  a += b;  a2 += b2;  d ^= a;  d2 ^= a2;                            \
-  d = rotl(d, 16);  d2 = rotl(d2, 16);                              \
-  c += d;  c2 += d2;  b ^= c;  b2 ^= c2;                            \
-  b = rotl(b, 12);  b2 = rotl(b2, 12);                              \
-  a += b;  a2 += b2;  d ^= a;  d2 ^= a2;                            \
-  d = rotl(d, 8);  d2 = rotl(d2, 8);                                \
-  c += d;  c2 += d2;  b ^= c;  b2 ^= c2;                            \
-  b = rotl(b, 7);  b2 = rotl(b2, 7)
 
 __device__ __forceinline__ void chacha12_pair_core(uint4 seed, uint4& r0,
                                                    uint4& r1) {
-  const u32 k0 = 0x65787061u, k1 = 0x6e642033u, k2 = 0x322d6279u,
-            k3 = 0x7465206bu;
-  u32 x0 = k0, x1 = k1, x2 = k2, x3 = k3;
-  u32 x4 = seed.w, x5 = seed.z, x6 = seed.y, x7 = seed.x;
-  u32 x8 = 0, x9 = 0, x10 = 0, x11 = 0, x12 = 0, x13 = 0, x14 = 0, x15 = 0;
-  u32 y0 = k0, y1 = k1, y2 = k2, y3 = k3;
-  u32 y4 = x4, y5 = x5, y6 = x6, y7 = x7;
-  u32 y8 = 0, y9 = 0, y10 = 0, y11 = 0, y12 = 0, y13 = 1, y14 = 0, y15 = 0;
-#pragma unroll
-  for (int r = 0; r < 6; ++r) {
-    CHACHA_QR2(x0, x4, x8, x12, y0, y4, y8, y12);
-    CHACHA_QR2(x1, x5, x9, x13, y1, y5, y9, y13);
-    CHACHA_QR2(x2, x6, x10, x14, y2, y6, y10, y14);
-    CHACHA_QR2(x3, x7, x11, x15, y3, y7, y11, y15);
-    CHACHA_QR2(x0, x5, x10, x15, y0, y5, y10, y15);
-    CHACHA_QR2(x1, x6, x11, x12, y1, y6, y11, y12);
-    CHACHA_QR2(x2, x7, x8, x13, y2, y7, y8, y13);
-    CHACHA_QR2(x3, x4, x9, x14, y3, y4, y9, y14);
-  }
-  r0 = make_uint4(x7 + seed.x, x6 + seed.y, x5 + seed.z, x4 + seed.w);
-  r1 = make_uint4(y7 + seed.x, y6 + seed.y, y5 + seed.z, y4 + seed.w);
+  u32 x[16][2];
+  chacha12<false>(seed, 0, x);
+  r0 = stream_out(x, 0, 7, seed);
+  r1 = stream_out(x, 1, 7, seed);
 }
-
-// Leaf-level variant: only out[7] = x7 + seed.x is needed.  Final
-// double-round cone: diagonal QR(x2,x7,x8,x13) needs its full chain;
-// its inputs need x2 (full col QR), x7 (full: b needs a,c,d), x8 (col
-// QR c through the second c+=d), x13 (col QR d through the second
-// d-rotate) — 56 ops instead of 96.
-#define CHACHA_QR2_C10(a, b, c, d, a2, b2, c2, d2) /* c final (skip last b) */ \
-  a += b;  a2 += b2;  d ^= a;  d2 ^= a2;                            \
-  d = rotl(d, 16);  d2 = rotl(d2, 16);                              \
-  c += d;  c2 += d2;  b ^= c;  b2 ^= c2;                            \
-  b = rotl(b, 12);  b2 = rotl(b2, 12);                              \
-  a += b;  a2 += b2;  d ^= a;  d2 ^= a2;                            \
-  d = rotl(d, 8);  d2 = rotl(d2, 8);                                \
-  c += d;  c2 += d2
-#define CHACHA_QR2_D10(a, b, c, d, a2, b2, c2, d2) /* d final (skip last c,b) */ \
-  a += b;  a2 += b2;  d ^= a;  d2 ^= a2;                            \
-  d = rotl(d, 16);  d2 = rotl(d2, 16);                              \
-  c += d;  c2 += d2;  b ^= c;  b2 ^= c2;                            \
-  b = rotl(b, 12);  b2 = rotl(b2, 12);                              \
-  a += b;  a2 += b2;  d ^= a;  d2 ^= a2;                            \
-  d = rotl(d, 8);  d2 = rotl(d2, 8)
 
 __device__ __forceinline__ void chacha12_pair_low_core(uint4 seed, u32& lo0,
                                                        u32& lo1) {
-  const u32 k0 = 0x65787061u, k1 = 0x6e642033u, k2 = 0x322d6279u,
-            k3 = 0x7465206bu;
-  u32 x0 = k0, x1 = k1, x2 = k2, x3 = k3;
-  u32 x4 = seed.w, x5 = seed.z, x6 = seed.y, x7 = seed.x;
-  u32 x8 = 0, x9 = 0, x10 = 0, x11 = 0, x12 = 0, x13 = 0, x14 = 0, x15 = 0;
-  u32 y0 = k0, y1 = k1, y2 = k2, y3 = k3;
-  u32 y4 = x4, y5 = x5, y6 = x6, y7 = x7;
-  u32 y8 = 0, y9 = 0, y10 = 0, y11 = 0, y12 = 0, y13 = 1, y14 = 0, y15 = 0;
-#pragma unroll
-  for (int r = 0; r < 5; ++r) {
-    CHACHA_QR2(x0, x4, x8, x12, y0, y4, y8, y12);
-    CHACHA_QR2(x1, x5, x9, x13, y1, y5, y9, y13);
-    CHACHA_QR2(x2, x6, x10, x14, y2, y6, y10, y14);
-    CHACHA_QR2(x3, x7, x11, x15, y3, y7, y11, y15);
-    CHACHA_QR2(x0, x5, x10, x15, y0, y5, y10, y15);
-    CHACHA_QR2(x1, x6, x11, x12, y1, y6, y11, y12);
-    CHACHA_QR2(x2, x7, x8, x13, y2, y7, y8, y13);
-    CHACHA_QR2(x3, x4, x9, x14, y3, y4, y9, y14);
-  }
-  // 6th double-round, pruned to the cone of x7/y7:
-  CHACHA_QR2_C10(x0, x4, x8, x12, y0, y4, y8, y12);   // x8 (c)
-  CHACHA_QR2_D10(x1, x5, x9, x13, y1, y5, y9, y13);   // x13 (d)
-  CHACHA_QR2(x2, x6, x10, x14, y2, y6, y10, y14);     // x2 (a: full)
-  CHACHA_QR2(x3, x7, x11, x15, y3, y7, y11, y15);     // x7 (b: full)
-  CHACHA_QR2(x2, x7, x8, x13, y2, y7, y8, y13);       // diagonal: x7 (b)
-  lo0 = x7 + seed.x;
-  lo1 = y7 + seed.x;
+  u32 x[16][2];
+  chacha12<true>(seed, 0, x);
+  lo0 = x[7][0] + seed.x;
+  lo1 = x[7][1] + seed.x;
 }
 
 // ---------------------------------------------------------------------------
@@ -287,9 +248,40 @@ __device__ __forceinline__ void chacha12_pair_low_core(uint4 seed, u32& lo0,
 //     table first in its dynamic LDS map.
 //   te0[x] bytes (MSB..LSB) = [2s, s, s, 3s];  te1 = ror8(te0),
 //   te2 = ror16, te3 = ror24;  sbox[x] = byte2 of te0[x].
+//
+// Everything that contract fixes is stated here: the table's size
+// (aes_lds_u32: what a launcher adds to its dynamic LDS and a kernel skips
+// to reach its own LDS), its staging (aes_stage_table) and the lane's
+// binding (AesLds::lane); aes_lds_init is the three together.
 // ---------------------------------------------------------------------------
+constexpr int AES_REP = 64;
+constexpr int AES_LDS_WORDS = 256 * AES_REP;  // 64 KiB
+
+// u32s of dynamic LDS the table takes in front of a kernel's own LDS map
+__host__ __device__ constexpr int aes_lds_u32(int prf) {
+  return prf == PRF_AES128 ? AES_LDS_WORDS : 0;
+}
+
+__device__ __forceinline__ u32 xor3(u32 a, u32 b, u32 c) {
+  return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96);  // a ^ b ^ c
+}
+
+// [S(a) S(b) S(c) S(d)] (MSB..LSB) from the four te0 words of a..d: sbox
+// is byte 2 of te0, gathered by two v_perm_b32 with disjoint bytes (the
+// caller xors the halves into its sum).
+__device__ __forceinline__ u32 aes_sb_hi(u32 ta, u32 tb) {
+  return __builtin_amdgcn_perm(ta, tb, 0x06020c0cu);
+}
+__device__ __forceinline__ u32 aes_sb_lo(u32 tc, u32 td) {
+  return __builtin_amdgcn_perm(tc, td, 0x0c0c0602u);
+}
+
 struct AesLds {
   u32 lane4;  // (threadIdx.x % 64) * 4
+  // The calling lane's copy of the table
+  static __device__ __forceinline__ AesLds lane() {
+    return AesLds{((u32)threadIdx.x & 63u) << 2};
+  }
   typedef __attribute__((address_space(3))) const u32 lds_u32;
   static __device__ __forceinline__ u32 ld(u32 byte_addr) {
     return *reinterpret_cast<lds_u32*>(byte_addr);
@@ -301,39 +293,42 @@ struct AesLds {
   }
   template <int K>
   __device__ __forceinline__ u32 te0_b(u32 w) const { return ld(addr_b<K>(w)); }
-  template <int K>
-  __device__ __forceinline__ u32 sbox_b(u32 w) const {
-    return (te0_b<K>(w) >> 16) & 0xff;
+  // One MixColumns output word: te0[a.b3] ^ te1[b.b2] ^ te2[c.b1] ^
+  // te3[d.b0] ^ k as two 3-input xors.
+  __device__ __forceinline__ u32 col(u32 a, u32 b, u32 c, u32 d, u32 k) const {
+    return xor3(xor3(te0_b<3>(a), rotr8(te0_b<2>(b)), rotr16(te0_b<1>(c))),
+                rotr24(te0_b<0>(d)), k);
   }
-  __device__ __forceinline__ u32 te0(u32 x) const { return ld((x << 8) | lane4); }
+  // One last-round output word: [S(a.b3) S(b.b2) S(c.b1) S(d.b0)] ^ k
+  __device__ __forceinline__ u32 last(u32 a, u32 b, u32 c, u32 d, u32 k) const {
+    return xor3(aes_sb_hi(te0_b<3>(a), te0_b<2>(b)),
+                aes_sb_lo(te0_b<1>(c), te0_b<0>(d)), k);
+  }
 };
 
 // Stage the replicated te0 table at LDS byte 0 (all threads of the
-// workgroup; the caller synchronizes).  `lds0` must be the start of the
-// kernel's dynamic LDS.  Word index e*64 + c => consecutive threads write
-// consecutive banks.
-__device__ __forceinline__ void aes_stage_table(u32* lds0,
-                                                const u32* __restrict__ aes_tabs) {
-  for (int idx = (int)threadIdx.x; idx < AES_LDS_WORDS; idx += (int)blockDim.x)
-    lds0[idx] = aes_tabs[idx >> 6];  // global layout: te0 at offset 0
+// workgroup; the caller synchronizes); nothing for the other PRFs.  `lds0`
+// must be the start of the kernel's dynamic LDS.  Word index e*64 + c =>
+// consecutive threads write consecutive banks.
+template <int PRF>
+__device__ __forceinline__ void aes_stage_table(
+    u32* lds0, const u32* __restrict__ aes_tabs) {
+  if constexpr (PRF == PRF_AES128) {
+    for (int idx = (int)threadIdx.x; idx < AES_LDS_WORDS;
+         idx += (int)blockDim.x)
+      lds0[idx] = aes_tabs[idx >> 6];  // global layout: te0 at offset 0
+  }
 }
 
-__device__ __forceinline__ u32 xor3(u32 a, u32 b, u32 c) {
-  return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96);  // a ^ b ^ c
+// The whole prologue of a kernel that stages nothing else: table, barrier
+// (AES only), lane binding.
+template <int PRF>
+__device__ __forceinline__ AesLds aes_lds_init(
+    u32* lds0, const u32* __restrict__ aes_tabs) {
+  aes_stage_table<PRF>(lds0, aes_tabs);
+  if constexpr (PRF == PRF_AES128) __syncthreads();
+  return AesLds::lane();
 }
-
-// [S(a) S(b) S(c) S(d)] (MSB..LSB) from the four te0 words of a..d: sbox
-// is byte 2 of te0, gathered by two v_perm_b32 with disjoint bytes (the
-// caller xors the halves into its sum).
-#define AES_SB_HI(ta, tb) __builtin_amdgcn_perm(ta, tb, 0x06020c0cu)
-#define AES_SB_LO(tc, td) __builtin_amdgcn_perm(tc, td, 0x0c0c0602u)
-
-// One MixColumns output word: te0[a.b3] ^ te1[b.b2] ^ te2[c.b1] ^
-// te3[d.b0] ^ k as two 3-input xors.
-#define AES_COL(T, a, b, c, d, k)                                         \
-  xor3(xor3((T).template te0_b<3>(a), rotr8((T).template te0_b<2>(b)),    \
-            rotr16((T).template te0_b<1>(c))),                            \
-       rotr24((T).template te0_b<0>(d)), k)
 
 // Both children (pos 0 and pos 1) with an ON-THE-FLY key schedule fused
 // into the interleaved cipher rounds: the key-expansion sbox chain (4
@@ -349,6 +344,14 @@ __device__ __forceinline__ void aes_cipher_pair(uint4 seed, const AesLds& T,
   u32 s0 = k0, s1 = k1, s2 = k2, s3 = k3;
   u32 u0 = (1u << 24) ^ k0, u1 = k1, u2 = k2, u3 = k3;
   u32 rcon = 0x01u;
+  // next round key (k0..k3 = rk[4r-4..4r-1] become rk[4r..4r+3])
+  auto next_round_key = [&] {
+    k0 = xor3(aes_sb_hi(T.te0_b<2>(k3), T.te0_b<1>(k3)),
+              aes_sb_lo(T.te0_b<0>(k3), T.te0_b<3>(k3)), k0) ^ (rcon << 24);
+    rcon = (rcon << 1) ^ ((rcon & 0x80u) ? 0x11bu : 0u);
+    rcon &= 0xffu;
+    k1 ^= k0; k2 ^= k1; k3 ^= k2;
+  };
   int r_begin = 1;
 #ifndef GPUDPF_AES_NOSHARE
   // Shared-prefix rounds: the two children's plaintexts (pos 0 / pos 1)
@@ -363,10 +366,11 @@ __device__ __forceinline__ void aes_cipher_pair(uint4 seed, const AesLds& T,
   {
     // round 1.  s3 == k3 here (the position byte only enters s0), so the
     // four te0 words of s3 the cipher round reads anyway also carry the
-    // sbox bytes of the round-1 key schedule: no separate sbox lookups.
+    // sbox bytes of the round-1 key schedule: no separate sbox lookups,
+    // hence no next_round_key.
     const u32 t33 = T.te0_b<3>(s3), t32 = T.te0_b<2>(s3),
               t31 = T.te0_b<1>(s3), t30 = T.te0_b<0>(s3);
-    k0 = xor3(AES_SB_HI(t32, t31), AES_SB_LO(t30, t33), k0) ^ (rcon << 24);
+    k0 = xor3(aes_sb_hi(t32, t31), aes_sb_lo(t30, t33), k0) ^ (rcon << 24);
     rcon = 0x02u;
     k1 ^= k0; k2 ^= k1; k3 ^= k2;
     const u32 a0 = T.addr_b<3>(s0);
@@ -383,10 +387,7 @@ __device__ __forceinline__ void aes_cipher_pair(uint4 seed, const AesLds& T,
     // address ^ 256
     const u32 m0 = xor3(n0, A, AesLds::ld(a0 ^ 256u));
     // round 2
-    k0 = xor3(AES_SB_HI(T.te0_b<2>(k3), T.te0_b<1>(k3)),
-              AES_SB_LO(T.te0_b<0>(k3), T.te0_b<3>(k3)), k0) ^ (rcon << 24);
-    rcon = 0x04u;
-    k1 ^= k0; k2 ^= k1; k3 ^= k2;
+    next_round_key();
     const u32 c0 = xor3(rotr8(T.te0_b<2>(n1)), rotr16(T.te0_b<1>(n2)),
                         rotr24(T.te0_b<0>(n3))) ^ k0;
     const u32 c1 = xor3(T.te0_b<3>(n1), rotr8(T.te0_b<2>(n2)),
@@ -408,46 +409,33 @@ __device__ __forceinline__ void aes_cipher_pair(uint4 seed, const AesLds& T,
 #endif
 #pragma unroll
   for (int r = r_begin; r < 10; ++r) {
-    // next round key (k0..k3 become rk[4r..4r+3])
-    k0 = xor3(AES_SB_HI(T.te0_b<2>(k3), T.te0_b<1>(k3)),
-              AES_SB_LO(T.te0_b<0>(k3), T.te0_b<3>(k3)), k0) ^ (rcon << 24);
-    rcon = (rcon << 1) ^ ((rcon & 0x80u) ? 0x11bu : 0u);
-    rcon &= 0xffu;
-    k1 ^= k0; k2 ^= k1; k3 ^= k2;
+    next_round_key();
     // cipher round r for both children
-    u32 n0 = AES_COL(T, s0, s1, s2, s3, k0);
-    u32 m0 = AES_COL(T, u0, u1, u2, u3, k0);
-    u32 n1 = AES_COL(T, s1, s2, s3, s0, k1);
-    u32 m1 = AES_COL(T, u1, u2, u3, u0, k1);
-    u32 n2 = AES_COL(T, s2, s3, s0, s1, k2);
-    u32 m2 = AES_COL(T, u2, u3, u0, u1, k2);
-    u32 n3 = AES_COL(T, s3, s0, s1, s2, k3);
-    u32 m3 = AES_COL(T, u3, u0, u1, u2, k3);
+    u32 n0 = T.col(s0, s1, s2, s3, k0);
+    u32 m0 = T.col(u0, u1, u2, u3, k0);
+    u32 n1 = T.col(s1, s2, s3, s0, k1);
+    u32 m1 = T.col(u1, u2, u3, u0, k1);
+    u32 n2 = T.col(s2, s3, s0, s1, k2);
+    u32 m2 = T.col(u2, u3, u0, u1, k2);
+    u32 n3 = T.col(s3, s0, s1, s2, k3);
+    u32 m3 = T.col(u3, u0, u1, u2, k3);
     s0 = n0; s1 = n1; s2 = n2; s3 = n3;
     u0 = m0; u1 = m1; u2 = m2; u3 = m3;
   }
-  // round-10 key
-  k0 = xor3(AES_SB_HI(T.te0_b<2>(k3), T.te0_b<1>(k3)),
-            AES_SB_LO(T.te0_b<0>(k3), T.te0_b<3>(k3)), k0) ^ (rcon << 24);
-  k1 ^= k0; k2 ^= k1; k3 ^= k2;
-  // last round: [S(a.b3) S(b.b2) S(c.b1) S(d.b0)] ^ k
-#define AES_LAST(a, b, c, d, k)                               \
-  xor3(AES_SB_HI(T.te0_b<3>(a), T.te0_b<2>(b)),               \
-       AES_SB_LO(T.te0_b<1>(c), T.te0_b<0>(d)), k)
-  u32 o0 = AES_LAST(s0, s1, s2, s3, k0);
-  u32 p0 = AES_LAST(u0, u1, u2, u3, k0);
+  next_round_key();  // round 10
+  u32 o0 = T.last(s0, s1, s2, s3, k0);
+  u32 p0 = T.last(u0, u1, u2, u3, k0);
   if constexpr (LOW) {
     ra = make_uint4(__builtin_bswap32(o0), 0, 0, 0);
     rb = make_uint4(__builtin_bswap32(p0), 0, 0, 0);
     return;
   }
-  u32 o1 = AES_LAST(s1, s2, s3, s0, k1);
-  u32 p1 = AES_LAST(u1, u2, u3, u0, k1);
-  u32 o2 = AES_LAST(s2, s3, s0, s1, k2);
-  u32 p2 = AES_LAST(u2, u3, u0, u1, k2);
-  u32 o3 = AES_LAST(s3, s0, s1, s2, k3);
-  u32 p3 = AES_LAST(u3, u0, u1, u2, k3);
-#undef AES_LAST
+  u32 o1 = T.last(s1, s2, s3, s0, k1);
+  u32 p1 = T.last(u1, u2, u3, u0, k1);
+  u32 o2 = T.last(s2, s3, s0, s1, k2);
+  u32 p2 = T.last(u2, u3, u0, u1, k2);
+  u32 o3 = T.last(s3, s0, s1, s2, k3);
+  u32 p3 = T.last(u3, u0, u1, u2, k3);
   ra = make_uint4(__builtin_bswap32(o0), __builtin_bswap32(o1),
                   __builtin_bswap32(o2), __builtin_bswap32(o3));
   rb = make_uint4(__builtin_bswap32(p0), __builtin_bswap32(p1),

@@ -113,6 +113,18 @@ def test_eval_scratch_bytes_matches_stack_placement():
                 (depth, batch)
 
 
+@pytest.mark.parametrize("depth,n", [(7, 256), (0, 1)])
+@pytest.mark.parametrize("prf", PRFS, ids=PRF_IDS.get)
+def test_naive_rejects_mismatched_domain(prf, depth, n):
+    """No GPU needed: the naive launcher checks depth against n, like its
+    siblings, before any HIP call, so null pointers never reach a kernel."""
+    if _hip is None:
+        pytest.skip("gpudpf._hip cannot be imported")
+    with pytest.raises(ValueError, match="bad depth/n"):
+        _hip.eval_naive(keys=0, out=0, aes_tabs=0, batch=1, n=n, depth=depth,
+                        prf=prf, stream=0)
+
+
 @functools.lru_cache(maxsize=None)
 def _table(depth):
     n = 1 << depth
