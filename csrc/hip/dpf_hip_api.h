@@ -5,7 +5,6 @@
 #pragma once
 #include <cstddef>
 #include <cstdint>
-#include <utility>
 
 namespace gpudpf_hip {
 
@@ -93,23 +92,28 @@ void launch_probe_prf(std::uintptr_t seeds, std::uintptr_t aes_tabs,
                       std::uintptr_t low0, std::uintptr_t low1, int count,
                       int prf, std::uintptr_t stream);
 
+// The three GEMMs.  Each splits K into `segs` slices of `kchunk` rows
+// (KSplit and the shared arithmetic: hip_util.h), and each *_split query is
+// the only place its launcher takes the split from: pure host arithmetic,
+// no HIP call, std::invalid_argument for a shape the launcher rejects.  The
+// launchers check shapes and pointers (non-null) before any HIP call.
+struct KSplit;
+
 // Exact u128 GEMM (research harness; gemm128.hip).  a: [M,K] u128 (as
-// 4xint32 limbs), bt: [N,K] u128, c: [M,N] u128, partials: device scratch
-// of gemm128_ksplit(M,N,K)*M*N u128.
-int gemm128_ksplit(long long M, long long N, long long K);
+// 4xint32 limbs), bt: [N,K] u128, c: [M,N] u128, partials: the caller's
+// device scratch of partials_bytes >= gemm128_split(M,N,K).segs*M*N*16.
+KSplit gemm128_split(long long M, long long N, long long K);
 void launch_gemm128(std::uintptr_t a, std::uintptr_t bt, std::uintptr_t c,
-                    std::uintptr_t partials, long long M, long long N,
-                    long long K, std::uintptr_t stream);
+                    std::uintptr_t partials, std::size_t partials_bytes,
+                    long long M, long long N, long long K,
+                    std::uintptr_t stream);
 
 // MFMA mod-2^32 GEMM (gemm_u32.hip): digit decomposition + i8 matrix
 // cores.  da/dbt: [4][M][K] / [4][N][K] int8 digit planes; c: [M][N] u32
 // (zeroed by caller; K-split partials combine with wrapping atomicAdd).
-// gemm_u32_split: the launcher's (ksplit, kchunk) — blockIdx.z slices of
-// kchunk (a multiple of 64) that together cover K; pure host arithmetic,
-// no HIP call.  Throws std::invalid_argument unless M%64, N%16 and K%64
-// are all 0.
-std::pair<long long, long long> gemm_u32_split(long long M, long long N,
-                                               long long K);
+// M%64, N%16 and K%64 must all be 0.  launch_digits writes the four planes
+// of `count` u32 words, count words apart (count == 0 launches nothing).
+KSplit gemm_u32_split(long long M, long long N, long long K);
 void launch_digits(std::uintptr_t in, std::uintptr_t out, long long count,
                    std::uintptr_t stream);
 void launch_gemm_u32_mfma(std::uintptr_t da, std::uintptr_t dbt,
@@ -119,7 +123,11 @@ void launch_gemm_u32_mfma(std::uintptr_t da, std::uintptr_t dbt,
 // Streaming mod-2^32 GEMM (gemm_stream.hip): reads the u32 table in place
 // (no transposed copy, no digit planes) — the huge-table wide-entry path.
 // a: [batch, K] u32 shares; b: [K, N] u32 table; c: [batch, N] u32
-// (zeroed by caller).  batch <= 16 (python wrapper chunks larger).
+// (zeroed by caller).  batch <= 16 (python wrapper chunks larger) and
+// N <= 65535*256.  Only this split drops the slices that would start at or
+// past K; its partials (segs*batch*N u32, in a per-device scratch) stay
+// within 1 GiB wherever one slice's do.
+KSplit gemm_u32_stream_split(int batch, long long K, long long N);
 void launch_gemm_u32_stream(std::uintptr_t a, std::uintptr_t b,
                             std::uintptr_t c, int batch, long long K,
                             long long N, std::uintptr_t stream);

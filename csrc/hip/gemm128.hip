@@ -92,33 +92,33 @@ __global__ void gemm128_reduce_kernel(const u128v* __restrict__ partials,
 
 }  // namespace
 
-int gemm128_ksplit(long long M, long long N, long long K) {
-  // fill ~4096 blocks; K-chunks are multiples of TK
-  long long xy = ((M + 15) / 16) * ((N + 15) / 16);
-  long long want = (4096 + xy - 1) / xy;
-  long long maxs = (K + TK - 1) / TK;
-  long long s = 1;
-  while (s * 2 <= want && s * 2 <= maxs) s *= 2;
-  return (int)s;
+KSplit gemm128_split(long long M, long long N, long long K) {
+  check_dims("gemm128", {M, N, K});
+  // fill ~4096 blocks with a power-of-two number of K slices
+  const long long xy = ((M + 15) / 16) * ((N + 15) / 16);
+  return split_k(K, (4096 + xy - 1) / xy, true);
 }
 
 void launch_gemm128(std::uintptr_t a, std::uintptr_t bt, std::uintptr_t c,
-                    std::uintptr_t partials, long long M, long long N,
-                    long long K, std::uintptr_t stream) {
-  const int ksplit = gemm128_ksplit(M, N, K);
-  long long kchunk = ((K + ksplit - 1) / ksplit + TK - 1) / TK * TK;
+                    std::uintptr_t partials, std::size_t partials_bytes,
+                    long long M, long long N, long long K,
+                    std::uintptr_t stream) {
+  const KSplit split = gemm128_split(M, N, K);
+  check_ptrs("gemm128", {a, bt, c, partials});
+  const long long MN = M * N;
+  if (partials_bytes < (std::size_t)split.segs * MN * sizeof(u128v))
+    throw std::invalid_argument("gemm128: partials smaller than segs*M*N u128");
   dim3 grid((unsigned)((M + 15) / 16), (unsigned)((N + 15) / 16),
-            (unsigned)ksplit);
+            (unsigned)split.segs);
   auto s = as_stream(stream);
   hipLaunchKernelGGL(gemm128_kernel, grid, dim3(256), 0, s,
                      as_ptr<const u128v>(a), as_ptr<const u128v>(bt),
-                     as_ptr<u128v>(partials), M, N, K, kchunk);
+                     as_ptr<u128v>(partials), M, N, K, split.kchunk);
   HIP_CHECK(hipGetLastError());
-  const long long MN = M * N;
   hipLaunchKernelGGL(gemm128_reduce_kernel,
                      dim3((unsigned)((MN + 255) / 256)), dim3(256), 0, s,
                      as_ptr<const u128v>(partials), as_ptr<u128v>(c), MN,
-                     ksplit);
+                     (int)split.segs);
   HIP_CHECK(hipGetLastError());
 }
 

@@ -202,49 +202,58 @@ __global__ __launch_bounds__(256) void gemm_u32_stream_reduce_kernel(
   c[i] += s;  // accumulate into caller's (zeroed or chunk-owned) output
 }
 
+long long col_tiles_of(long long N) {
+  return (N + kColsPerTile - 1) / kColsPerTile;
+}
+
 template <int B>
 void launch_b(const u32* a, const u32* b, u32* c, int batch, long long K,
-              long long N, hipStream_t st) {
-  const long long col_tiles = (N + kColsPerTile - 1) / kColsPerTile;
-  // k-split: >= 4096 single-wave workgroups (16 waves/CU)
-  long long segs = (4096 + col_tiles - 1) / col_tiles;
-  long long max_segs = (K + kChunkK - 1) / kChunkK;
-  if (segs > max_segs) segs = max_segs;
-  // bound the partials scratch at 1 GiB
-  const long long max_by_mem = ((long long)1 << 30) / ((long long)batch * N * 4);
-  if (segs > max_by_mem && max_by_mem >= 1) segs = max_by_mem;
-  if (segs < 1) segs = 1;
-  long long k_seg = ((K + segs - 1) / segs + kChunkK - 1) / kChunkK * kChunkK;
-  segs = (K + k_seg - 1) / k_seg;
-  u32* part =
-      static_cast<u32*>(g_partials.get((size_t)segs * batch * N * 4));
-  hipLaunchKernelGGL(gemm_u32_stream_kernel<B>,
-                     dim3((unsigned)segs, (unsigned)col_tiles),
-                     dim3(kThreads), 0, st, a, b, part, batch, K, N, k_seg,
-                     col_tiles);
-  HIP_CHECK(hipGetLastError());
+              long long N, KSplit split, hipStream_t st) {
   const long long elems = (long long)batch * N;
+  u32* part =
+      static_cast<u32*>(g_partials.get((size_t)split.segs * elems * 4));
+  hipLaunchKernelGGL(gemm_u32_stream_kernel<B>,
+                     dim3((unsigned)split.segs, (unsigned)col_tiles_of(N)),
+                     dim3(kThreads), 0, st, a, b, part, batch, K, N,
+                     split.kchunk, col_tiles_of(N));
+  HIP_CHECK(hipGetLastError());
   hipLaunchKernelGGL(gemm_u32_stream_reduce_kernel,
                      dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, st,
-                     part, c, elems, segs);
+                     part, c, elems, split.segs);
   HIP_CHECK(hipGetLastError());
 }
 
 }  // namespace
 
-void launch_gemm_u32_stream(std::uintptr_t a, std::uintptr_t b,
-                            std::uintptr_t c, int batch, long long K,
-                            long long N, std::uintptr_t stream) {
+KSplit gemm_u32_stream_split(int batch, long long K, long long N) {
   if (batch < 1 || batch > kMaxB)
     throw std::invalid_argument("stream GEMM batch must be 1..16 "
                                 "(python wrapper chunks larger batches)");
+  check_dims("stream GEMM", {K, N});
+  // >= 4096 single-wave workgroups (16 waves/CU), but at most 1 GiB of
+  // partials unless a single slice's already exceed that
+  long long want = (4096 + col_tiles_of(N) - 1) / col_tiles_of(N);
+  const long long max_by_mem = ((long long)1 << 30) / ((long long)batch * N * 4);
+  if (max_by_mem >= 1 && want > max_by_mem) want = max_by_mem;
+  KSplit s = split_k(K, want, false);
+  s.segs = (K + s.kchunk - 1) / s.kchunk;  // no slice starts at or past K
+  return s;
+}
+
+void launch_gemm_u32_stream(std::uintptr_t a, std::uintptr_t b,
+                            std::uintptr_t c, int batch, long long K,
+                            long long N, std::uintptr_t stream) {
+  const KSplit split = gemm_u32_stream_split(batch, K, N);
+  if (col_tiles_of(N) > 65535)
+    throw std::invalid_argument("stream GEMM: N exceeds 65535 column tiles");
+  check_ptrs("stream GEMM", {a, b, c});
   auto* ap = as_ptr<const u32>(a);
   auto* bp = as_ptr<const u32>(b);
   auto* cp = as_ptr<u32>(c);
   auto st = as_stream(stream);
-  if (batch <= 4) launch_b<4>(ap, bp, cp, batch, K, N, st);
-  else if (batch <= 8) launch_b<8>(ap, bp, cp, batch, K, N, st);
-  else launch_b<16>(ap, bp, cp, batch, K, N, st);
+  if (batch <= 4) launch_b<4>(ap, bp, cp, batch, K, N, split, st);
+  else if (batch <= 8) launch_b<8>(ap, bp, cp, batch, K, N, split, st);
+  else launch_b<16>(ap, bp, cp, batch, K, N, split, st);
 }
 
 }  // namespace gpudpf_hip

@@ -22,7 +22,6 @@
 #include <hip/hip_runtime.h>
 
 #include <stdexcept>
-#include <utility>
 
 #include "dpf_hip_api.h"
 #include "hip_util.h"
@@ -116,6 +115,9 @@ __global__ __launch_bounds__(256) void gemm_u32_mfma_kernel(
 
 void launch_digits(std::uintptr_t in, std::uintptr_t out, long long count,
                    std::uintptr_t stream) {
+  if (count < 0) throw std::invalid_argument("digits: count must be >= 0");
+  if (count == 0) return;  // nothing to write, and no zero-block grid
+  check_ptrs("digits", {in, out});
   long long blocks = (count + 255) / 256;
   if (blocks > (1 << 20)) blocks = 1 << 20;  // grid-stride beyond this
   hipLaunchKernelGGL(digits_kernel, dim3((unsigned)blocks), dim3(256), 0,
@@ -124,34 +126,26 @@ void launch_digits(std::uintptr_t in, std::uintptr_t out, long long count,
   HIP_CHECK(hipGetLastError());
 }
 
-std::pair<long long, long long> gemm_u32_split(long long M, long long N,
-                                               long long K) {
+KSplit gemm_u32_split(long long M, long long N, long long K) {
   if (M <= 0 || N <= 0 || K <= 0 || M % 64 || N % 16 || K % 64)
     throw std::invalid_argument("gemm_u32: M%64, N%16, K%64 must be 0");
-  // fill ~1024 workgroups; ksplit is a power of two, K-chunks are whole
-  // 64-deep MFMA steps
-  long long xy = (M / 64) * (N / 16);
-  long long want = (1024 + xy - 1) / xy;
-  long long maxs = K / 64;
-  long long ks = 1;
-  while (ks * 2 <= want && ks * 2 <= maxs) ks *= 2;
-  // ceil on both divisions: with floor(K / ks) the slices stop short of K
-  // whenever floor(K / ks) is a multiple of 64 and ks does not divide K.
-  // Slices that start at or past K add zero.
-  long long kchunk = ((K + ks - 1) / ks + 63) / 64 * 64;
-  return {ks, kchunk};
+  // fill ~1024 workgroups with a power-of-two number of K slices, each a
+  // whole number of 64-deep MFMA steps
+  const long long xy = (M / 64) * (N / 16);
+  return split_k(K, (1024 + xy - 1) / xy, true);
 }
 
 void launch_gemm_u32_mfma(std::uintptr_t da, std::uintptr_t dbt,
                           std::uintptr_t c, long long M, long long N,
                           long long K, std::uintptr_t stream) {
-  const auto split = gemm_u32_split(M, N, K);
-  const long long ks = split.first, kchunk = split.second;
+  const KSplit split = gemm_u32_split(M, N, K);
+  check_ptrs("gemm_u32", {da, dbt, c});
   hipLaunchKernelGGL(gemm_u32_mfma_kernel,
                      dim3((unsigned)(M / 64), (unsigned)(N / 16),
-                          (unsigned)ks),
+                          (unsigned)split.segs),
                      dim3(256), 0, as_stream(stream), as_ptr<const s8>(da),
-                     as_ptr<const s8>(dbt), as_ptr<u32>(c), M, N, K, kchunk);
+                     as_ptr<const s8>(dbt), as_ptr<u32>(c), M, N, K,
+                     split.kchunk);
   HIP_CHECK(hipGetLastError());
 }
 

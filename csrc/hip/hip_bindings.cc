@@ -46,6 +46,15 @@ int device_count() {
   return n;
 }
 
+// A K-split query, bound as a function returning the tuple (segs, kchunk).
+template <class... A>
+auto split_tuple(gpudpf_hip::KSplit (*query)(A...)) {
+  return [query](A... args) {
+    const gpudpf_hip::KSplit s = query(args...);
+    return std::make_pair(s.segs, s.kchunk);
+  };
+}
+
 }  // namespace
 
 PYBIND11_MODULE(_hip, m) {
@@ -87,10 +96,11 @@ PYBIND11_MODULE(_hip, m) {
         py::arg("depth"), py::arg("prf"), py::arg("stream"),
         py::call_guard<py::gil_scoped_release>());
   m.def("gemm128", &gpudpf_hip::launch_gemm128, py::arg("a"), py::arg("bt"),
-        py::arg("c"), py::arg("partials"), py::arg("m"), py::arg("n"),
-        py::arg("k"), py::arg("stream"),
+        py::arg("c"), py::arg("partials"), py::arg("partials_bytes"),
+        py::arg("m"), py::arg("n"), py::arg("k"), py::arg("stream"),
         py::call_guard<py::gil_scoped_release>());
-  m.def("gemm128_ksplit", &gpudpf_hip::gemm128_ksplit);
+  m.def("gemm128_split", split_tuple(&gpudpf_hip::gemm128_split),
+        py::arg("m"), py::arg("n"), py::arg("k"));
   m.def("prf_sol", &gpudpf_hip::launch_prf_sol, py::arg("aes_tabs"),
         py::arg("out"), py::arg("blocks"), py::arg("iters"), py::arg("prf"),
         py::arg("stream"), py::call_guard<py::gil_scoped_release>());
@@ -100,12 +110,15 @@ PYBIND11_MODULE(_hip, m) {
   m.def("gemm_u32_mfma", &gpudpf_hip::launch_gemm_u32_mfma, py::arg("da"),
         py::arg("dbt"), py::arg("c"), py::arg("m"), py::arg("n"), py::arg("k"),
         py::arg("stream"), py::call_guard<py::gil_scoped_release>());
-  m.def("gemm_u32_split", &gpudpf_hip::gemm_u32_split, py::arg("m"),
-        py::arg("n"), py::arg("k"));
+  m.def("gemm_u32_split", split_tuple(&gpudpf_hip::gemm_u32_split),
+        py::arg("m"), py::arg("n"), py::arg("k"));
   m.def("gemm_u32_stream", &gpudpf_hip::launch_gemm_u32_stream, py::arg("a"),
         py::arg("b"), py::arg("c"), py::arg("batch"), py::arg("k"),
         py::arg("n"), py::arg("stream"),
         py::call_guard<py::gil_scoped_release>());
+  m.def("gemm_u32_stream_split",
+        split_tuple(&gpudpf_hip::gemm_u32_stream_split), py::arg("batch"),
+        py::arg("k"), py::arg("n"));
   m.def("probe_alu", &gpudpf_hip::launch_probe_alu, py::arg("a"), py::arg("b"),
         py::arg("add_out"), py::arg("mul_out"), py::arg("count"),
         py::arg("stream"), py::call_guard<py::gil_scoped_release>());

@@ -1,12 +1,14 @@
 // Host-side helpers shared by the HIP translation units of gpudpf._hip:
 // error checking, typed views of the launchers' integer arguments, the
-// domain check, the large-LDS opt-in, runtime -> compile-time PRF dispatch
-// and the grow-only device scratch.  Internal: not part of dpf_hip_api.h.
+// domain check, the GEMMs' argument checks and K-split, the large-LDS
+// opt-in, runtime -> compile-time PRF dispatch and the grow-only device
+// scratch.  Internal: not part of dpf_hip_api.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
 #include <cstdint>
+#include <initializer_list>
 #include <mutex>
 #include <set>
 #include <stdexcept>
@@ -54,6 +56,37 @@ inline hipStream_t as_stream(std::uintptr_t s) {
 inline void check_domain(int depth, long long n) {
   if (depth < 1 || ((long long)1 << depth) != n)
     throw std::invalid_argument("bad depth/n");
+}
+
+// Launch-argument checks of the GEMM launchers, made before any HIP call.
+inline void check_ptrs(const char* what,
+                       std::initializer_list<std::uintptr_t> ptrs) {
+  for (std::uintptr_t p : ptrs)
+    if (!p) throw std::invalid_argument(std::string(what) + ": null pointer");
+}
+inline void check_dims(const char* what, std::initializer_list<long long> dims) {
+  for (long long d : dims)
+    if (d < 1)
+      throw std::invalid_argument(std::string(what) +
+                                  ": dimensions must be >= 1");
+}
+
+// A GEMM's K-split: slice i of `segs` covers rows [i*kchunk, (i+1)*kchunk)
+// of K, clipped to K; kchunk is a multiple of the kernels' 64-row K step.
+struct KSplit {
+  long long segs, kchunk;
+};
+
+// `want` slices clamped to [1, ceil(K/64)], floored to a power of two if
+// `pow2`, each ceil(K/segs) rows rounded up to 64 (ceil on both divisions:
+// with floor(K/segs) the slices can stop short of K).  segs*kchunk >= K;
+// trailing slices may start at or past K and add zero.
+inline KSplit split_k(long long K, long long want, bool pow2) {
+  const long long max_segs = (K + 63) / 64;
+  long long segs = want < 1 ? 1 : want > max_segs ? max_segs : want;
+  if (pow2)
+    while (segs & (segs - 1)) segs &= segs - 1;  // keep the top bit
+  return {segs, ((K + segs - 1) / segs + 63) / 64 * 64};
 }
 
 // Launches that ask for 64 KiB or more of dynamic LDS (every kernel that

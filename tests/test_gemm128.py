@@ -135,7 +135,7 @@ def _check_gpu(got, a, bt, want, tag):
 @pytest.mark.parametrize("M,N,K", GPU_SHAPES, ids=lambda v: str(v))
 def test_gemm128_gpu_edge_shapes(M, N, K, kind):
     if (M, N, K) == (16, 16, 8256):
-        assert _hip.gemm128_ksplit(M, N, K) == 128
+        assert _hip.gemm128_split(M, N, K)[0] == 128
     a, bt, want = _case(kind, M, N, K)
     got = ops.gemm128(torch.from_numpy(a), torch.from_numpy(bt))
     _check_gpu(got, a, bt, want, (M, N, K, kind))
@@ -151,11 +151,32 @@ def test_gemm128_gpu_poisoned_scratch(M, N, K, kind):
     dev = torch.device("cuda:0")
     a_g = torch.from_numpy(a).to(dev)
     b_g = torch.from_numpy(bt).to(dev)
-    ksplit = _hip.gemm128_ksplit(M, N, K)
+    ksplit = _hip.gemm128_split(M, N, K)[0]
     scratch = torch.full((ksplit, M, N, 4), POISON, dtype=torch.int32,
                          device=dev)
     c_g = torch.full((M, N, 4), POISON, dtype=torch.int32, device=dev)
     _hip.gemm128(a_g.data_ptr(), b_g.data_ptr(), c_g.data_ptr(),
-                 scratch.data_ptr(), M, N, K,
+                 scratch.data_ptr(), scratch.numel() * 4, M, N, K,
                  torch.cuda.current_stream(dev).cuda_stream)
     _check_gpu(c_g, a, bt, want, (M, N, K, kind))
+
+
+@pytest.mark.gpu
+def test_gemm128_gpu_rejects_short_partials():
+    """Partials one u128 short of ksplit*M*N: nothing is launched."""
+    M, N, K = 16, 16, 8256
+    a, bt, _ = _case("random", M, N, K)
+    dev = torch.device("cuda:0")
+    a_g = torch.from_numpy(a).to(dev)
+    b_g = torch.from_numpy(bt).to(dev)
+    ksplit = _hip.gemm128_split(M, N, K)[0]
+    assert ksplit == 128
+    scratch = torch.full((ksplit * M * N - 1, 4), POISON, dtype=torch.int32,
+                         device=dev)
+    c_g = torch.full((M, N, 4), POISON, dtype=torch.int32, device=dev)
+    with pytest.raises(ValueError):
+        _hip.gemm128(a_g.data_ptr(), b_g.data_ptr(), c_g.data_ptr(),
+                     scratch.data_ptr(), scratch.numel() * 4, M, N, K,
+                     torch.cuda.current_stream(dev).cuda_stream)
+    torch.cuda.synchronize(dev)
+    assert bool((c_g == POISON).all()) and bool((scratch == POISON).all())
