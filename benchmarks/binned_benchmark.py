@@ -16,7 +16,9 @@ serving step (key H2D, kernel(s), share D2H) in three set-ups:
 
 Per set-up: warm-up steps, then `--windows` timed windows of at least
 `--window-s` seconds each, all ending in a synchronise; the median window
-is reported with the minimum and maximum.  The binned and loop shares are
+is reported with the minimum and maximum.  `--entry-words` (16, 32, 48 or
+64; default 16) is the row width of every table: wider than 16 words all
+three set-ups run the wide fused kernel (fused_words).  The binned and loop shares are
 compared once, exactly.  One dict line per (config, set-up), then one per
 config with the ratios; benchmarks/scrape.py reads them.
 """
@@ -36,9 +38,9 @@ from gpudpf import BinnedDPF, DPF
 from gpudpf.serving import PipelinedServer
 
 
-def rand_table(rows, seed):
+def rand_table(rows, seed, words=16):
     g = torch.Generator().manual_seed(seed)
-    return torch.randint(-(2**31), 2**31, (rows, 16), dtype=torch.int64,
+    return torch.randint(-(2**31), 2**31, (rows, words), dtype=torch.int64,
                          generator=g).to(torch.int32)
 
 
@@ -84,6 +86,8 @@ def main():
     ap.add_argument("--requests", type=int, nargs="+", default=[1, 8])
     ap.add_argument("--prfs", nargs="+",
                     default=["AES128", "CHACHA20", "SALSA20"])
+    ap.add_argument("--entry-words", type=int, default=16,
+                    choices=list(DPF.FUSED_WIDTHS))
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--windows", type=int, default=3)
     ap.add_argument("--window-s", type=float, default=0.4)
@@ -95,18 +99,19 @@ def main():
     for num_bins in a.bins:
         for logn in a.logn:
             n = 1 << logn
-            tables = [rand_table(n, 100 * logn + b) for b in range(num_bins)]
+            tables = [rand_table(n, 100 * logn + b, a.entry_words)
+                      for b in range(num_bins)]
             mono_table = torch.cat(tables)
             for prf_name in a.prfs:
                 prf = getattr(DPF, "PRF_" + prf_name)
-                binned = BinnedDPF(prf=prf)
+                binned = BinnedDPF(prf=prf, fused_words=a.entry_words)
                 binned.eval_init(tables)
                 loop = []
                 for t in tables:
-                    d = DPF(prf=prf)
+                    d = DPF(prf=prf, fused_words=a.entry_words)
                     d.eval_init(t)
                     loop.append(d)
-                mono = DPF(prf=prf)
+                mono = DPF(prf=prf, fused_words=a.entry_words)
                 mono.eval_init(mono_table)
                 for requests in a.requests:
                     run(a, dev, prf_name, num_bins, n, requests, binned,
@@ -133,8 +138,10 @@ def run(a, dev, prf_name, num_bins, n, requests, binned, loop, mono):
 
     keys_pinned = keys.clone().pin_memory()
     keys_gpu = torch.zeros_like(keys, device=dev)
-    out_gpu = torch.zeros((batch, 16), dtype=torch.int32, device=dev)
-    out_pinned = torch.zeros((batch, 16), dtype=torch.int32).pin_memory()
+    out_gpu = torch.zeros((batch, a.entry_words), dtype=torch.int32,
+                          device=dev)
+    out_pinned = torch.zeros((batch, a.entry_words),
+                             dtype=torch.int32).pin_memory()
 
     def loop_step():
         keys_pinned.numpy()[:] = keys.numpy()
@@ -157,7 +164,7 @@ def run(a, dev, prf_name, num_bins, n, requests, binned, loop, mono):
     del srv
 
     cfg = {"prf": prf_name, "num_bins": num_bins, "bin_n": n,
-           "requests": requests, "keys": batch}
+           "entry_words": a.entry_words, "requests": requests, "keys": batch}
     for setup, (med, lo, hi, steps) in res.items():
         print(dict(cfg, setup=setup, ms_per_step=round(med, 4),
                    ms_min=round(lo, 4), ms_max=round(hi, 4),

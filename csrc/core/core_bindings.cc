@@ -395,6 +395,7 @@ PYBIND11_MODULE(_core, m) {
   m.def("grid_expand", &grid_expand, py::arg("key"), py::arg("prf_method"));
   m.attr("KEY_INTS") = py::int_(kKeyInts);
   m.attr("ENTRY_WORDS") = py::int_(kEntryWords);
+  m.attr("MAX_FUSED_WORDS") = py::int_(kMaxFusedWords);
   m.attr("PRF_DUMMY") = py::int_((int)PRF_DUMMY);
   m.attr("PRF_SALSA20") = py::int_((int)PRF_SALSA20);
   m.attr("PRF_CHACHA20") = py::int_((int)PRF_CHACHA20);

@@ -85,6 +85,9 @@ void aes128_encrypt2_ni(const AesNiRoundKeys& rk, unsigned char out0[16],
 constexpr int kMaxDepth = 32;
 constexpr int kKeyInts = 524;   // serialized size in int32 (2096 bytes)
 constexpr int kEntryWords = 16; // table entry = 16 x u32 (padded)
+// Widest padded table row (u32) the fused kernel serves: 4 blocks of
+// kEntryWords.  The one statement of that limit (kernel, launchers, python).
+constexpr int kMaxFusedWords = 4 * kEntryWords;
 // Wire layout in int32 offsets (slot s = ints [4s, 4s+4)): correction word
 // cw[sel][level*2 + bit] is u128 slot 1 + sel*kCwPerSel + level*2 + bit.
 constexpr int kCwPerSel = 2 * kMaxDepth;  // correction words per selector

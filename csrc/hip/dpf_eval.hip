@@ -38,6 +38,11 @@
 //     contiguous 32 KB slab; every lane reads its two rows as 8 contiguous
 //     dwordx4 loads.  All workgroups stream the table in the same order
 //     => cross-key reuse in L2/LLC.
+//   * Wide rows: the fused kernel has a compile-time row width of W 16-word
+//     blocks (rows of 16*W <= MAX_FUSED_WORDS u32).  A leaf pair's shares
+//     are computed once and MACed into all 16*W columns; the rows are
+//     loaded one column block at a time, the first before the leaf cipher
+//     and each further one ahead of the previous block's MACs.
 //
 // This file holds the production DFS kernel and its launchers.  The device
 // PRFs are in prf_device.h; the naive / BFS / cooperative strategies in
@@ -63,6 +68,32 @@ GrowScratch g_eval_scratch;
 constexpr int MAX_LDS_LEVELS = 4;
 // Most (key, segment) units one AES workgroup walks (they share the table)
 constexpr int AES_MAX_UNITS = 4;
+// The same for rows wider than 16 words.  The K = 4 kernel lives in 128
+// VGPRs and uses 127 of them at 16 words, so it has no room for the 16*W
+// accumulators of a wide row; at K <= 2 a workgroup is at most 8 waves and
+// a wave may take 256.
+constexpr int AES_MAX_UNITS_WIDE = 2;
+// Widest table row (u32) the fused kernel serves: W <= 4 column blocks
+constexpr int MAX_FUSED_WORDS = gpudpf::kMaxFusedWords;
+
+// Runtime row width -> compile-time column-block count W: calls
+// f(std::integral_constant<int, W>{}) for rows of 16*W words, as with_prf
+// does for the PRF.  The only statement of the widths the kernel serves.
+template <class F>
+void with_row_blocks(int entry_words, F&& f) {
+  static_assert(MAX_FUSED_WORDS == 64, "one case per 16-word block");
+  switch (entry_words) {
+    case 16: f(std::integral_constant<int, 1>{}); break;
+    case 32: f(std::integral_constant<int, 2>{}); break;
+    case 48: f(std::integral_constant<int, 3>{}); break;
+    case 64: f(std::integral_constant<int, 4>{}); break;
+    default:
+      throw std::invalid_argument("entry_words must be 16, 32, 48 or 64");
+  }
+}
+inline void check_entry_words(int entry_words) {
+  with_row_blocks(entry_words, [](auto) {});
+}
 
 // Geometry of one eval launch, the single statement of where every
 // sibling-stack level lives and how large the LDS and scratch slices are.
@@ -83,7 +114,9 @@ struct EvalGeom {
   int shared_u4;    // uint4s of the ping-pong / LDS-stack region of a unit
   int unit_u32;     // u32s of one unit's LDS slice: cw | shared | red
 
-  __host__ __device__ EvalGeom(int depth, int zlog)
+  // W: 16-word column blocks of a table row (1 for the expand kernel).
+  // Only the reduction slice depends on it; the scratch does not.
+  __host__ __device__ EvalGeom(int depth, int zlog, int W)
       : Z(1 << zlog),
         DS(depth - zlog),
         lds_levels(DS > 3 ? (DS - 3 < MAX_LDS_LEVELS ? DS - 3 : MAX_LDS_LEVELS)
@@ -93,10 +126,11 @@ struct EvalGeom {
         // the 64-bit scratch row offset has a non-negative factor
         glob_levels((DS - 3) - lds_levels > 0 ? (DS - 3) - lds_levels : 0),
         shared_u4(Z * (lds_levels > 2 ? lds_levels : 2)),
-        unit_u32((2 * kCwPerSel + shared_u4) * 4 + (Z >> 6) * 16) {}
+        unit_u32((2 * kCwPerSel + shared_u4) * 4 + (Z >> 6) * 16 * W) {}
 
   // Dynamic LDS bytes of a workgroup of K units: the replicated AES table
-  // in front of the unit slices
+  // in front of the unit slices.  Largest: AES, K = 4, W = 1 at 137 KiB
+  // (wide AES, K = 2, W = 4: 102 KiB), within the CU's 160 KiB.
   std::size_t lds_bytes(int prf, int K) const {
     return ((std::size_t)aes_lds_u32(prf) + (std::size_t)K * unit_u32) * 4;
   }
@@ -136,7 +170,7 @@ __device__ __forceinline__ void expand_pair(uint4 seed, int i,
 // one 64 KiB te0 table so the table does not cost occupancy).  Dynamic LDS
 // map (the kernel has no static LDS, so it starts at LDS byte 0):
 //   [aes: 0/16384 u32] then K unit slices of
-//   [cw: 128 uint4][shared: Z*max(2, min(DS-3, 4)) uint4][red: Z/64*16 u32]
+//   [cw: 128 uint4][shared: Z*max(2, min(DS-3, 4)) uint4][red: Z/64*16*W u32]
 // The `shared` region is the phase-1 ping-pong (2*Z uint4) first, then the
 // cold DFS stack (LDS levels) — never live simultaneously.
 // Hot stack levels DS-1 / DS-2 are the registers rtop1 / rtop2.
@@ -169,9 +203,18 @@ __device__ __forceinline__ void expand_pair(uint4 seed, int i,
 // [0, num_bins)) arrive as an argument pack that is empty for the unbinned
 // instantiations: an argument of any type, even an empty struct, would move
 // their hidden kernel arguments and change their code.
+//
+// W (FUSED only): table rows and `out` rows are 16*W u32.  Row stride,
+// bin-block stride, accumulators, reduction slice and atomics scale with
+// it; phase 1, the descent, the stacks and the scratch do not.  Per step
+// the leaf pair's (v0, v1) is computed once and MACed into all 16*W
+// columns.  The two rows are loaded in 16-word column blocks (4 dwordx4 per
+// row): block 0 before the leaf cipher, which hides it, and block c+1 just
+// ahead of block c's 32 MACs, so at most two blocks (64 VGPRs) of row data
+// are in flight beside the 16*W accumulators, not all 8*W loads.
 __device__ __forceinline__ const int* bin_ids(const int* ids) { return ids; }
 
-template <int PRF, bool FUSED, int K, class... Bins>
+template <int PRF, bool FUSED, int K, int W, class... Bins>
 __global__ __launch_bounds__(256 * K) void dpf_eval_kernel(
     const int* __restrict__ keys, const u32* __restrict__ table,
     u32* __restrict__ out, const u32* __restrict__ aes_tabs,
@@ -179,8 +222,12 @@ __global__ __launch_bounds__(256 * K) void dpf_eval_kernel(
     long long n, Bins... bins) {
   constexpr bool BINNED = sizeof...(Bins) == 1;
   static_assert(BINNED ? FUSED : sizeof...(Bins) == 0, "bins: one const int*");
+  static_assert(W >= 1 && 16 * W <= MAX_FUSED_WORDS && (FUSED || W == 1),
+                "rows of 16*W words, wide only when fused");
+  static_assert(W == 1 || K <= AES_MAX_UNITS_WIDE, "wide rows: K <= 2");
+  constexpr int ROW = 16 * W;  // u32 per table row and per out row
   extern __shared__ u32 smem[];
-  const EvalGeom g(depth, zlog);
+  const EvalGeom g(depth, zlog, W);
   const int Z = g.Z, DS = g.DS, lds_base = g.lds_base;
   const int t = (int)threadIdx.x & (Z - 1);
   const int u_local = K == 1 ? 0 : (int)threadIdx.x >> zlog;
@@ -229,9 +276,9 @@ __global__ __launch_bounds__(256 * K) void dpf_eval_kernel(
   __syncthreads();  // everyone holds their frontier seed; pp is now free
   uint4* stack = shared_region;  // LDS stack levels [lds_base, DS-3]
 
-  u32 acc[16];
+  u32 acc[ROW];
 #pragma unroll
-  for (int w = 0; w < 16; ++w) acc[w] = 0;
+  for (int w = 0; w < ROW; ++w) acc[w] = 0;
 
   if (active) {
     // Targeted descent to leaf-pair j_lo: at split d take bit (DS-1-d) of
@@ -270,22 +317,27 @@ __global__ __launch_bounds__(256 * K) void dpf_eval_kernel(
     if constexpr (BINNED) {
       const u32 bin = __builtin_amdgcn_readfirstlane(
           (u32)bin_ids(bins...)[key_id]);
-      table += (unsigned long long)bin * (unsigned long long)n * 16ull;
+      table += (unsigned long long)bin * (unsigned long long)n *
+               (unsigned long long)ROW;
     }
 
     for (long long j = j_lo; j < j_hi; ++j) {
-      // Issue the two table-row loads first: the leaf ciphers below hide
-      // their latency.
-      uint4 r0q[4], r1q[4];
-      if constexpr (FUSED) {
-        const uint4* rows =
-            reinterpret_cast<const uint4*>(table + ((j << (zlog + 1)) +
-                                                    ((long long)t << 1)) * 16);
+      // Issue the first column block of the two table rows first: the
+      // leaf ciphers below hide its latency.  rq[cb & 1][b] holds column
+      // block cb of row b.
+      uint4 rq[2][2][4];
+      const uint4* rows = nullptr;
+      auto load_block = [&](int cb) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-          r0q[q] = rows[q];
-          r1q[q] = rows[q + 4];
+          rq[cb & 1][0][q] = rows[4 * cb + q];
+          rq[cb & 1][1][q] = rows[4 * (W + cb) + q];
         }
+      };
+      if constexpr (FUSED) {
+        rows = reinterpret_cast<const uint4*>(
+            table + ((j << (zlog + 1)) + ((long long)t << 1)) * ROW);
+        load_block(0);
       }
 
       u32 v0, v1;
@@ -299,11 +351,36 @@ __global__ __launch_bounds__(256 * K) void dpf_eval_kernel(
 
       if constexpr (FUSED) {
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          acc[4 * q + 0] += v0 * r0q[q].x + v1 * r1q[q].x;
-          acc[4 * q + 1] += v0 * r0q[q].y + v1 * r1q[q].y;
-          acc[4 * q + 2] += v0 * r0q[q].z + v1 * r1q[q].z;
-          acc[4 * q + 3] += v0 * r0q[q].w + v1 * r1q[q].w;
+        for (int cb = 0; cb < W; ++cb) {
+          u32* acc_c = acc + 16 * cb;
+          if constexpr (W > 1) if (cb + 1 < W) {
+            // Block cb+1 is in flight during block cb's MACs and no sooner.
+            // Left alone the compiler issues all 8*W loads ahead of the
+            // cipher (128 VGPRs of row data at W = 4, which spills the AES
+            // K = 2 kernel), so the address of a further block is made to
+            // depend on what frees its registers: the leaf shares for
+            // block 1, the sums of block cb-1 after that.  The statement
+            // emits no instruction.
+            int tt = t;
+            if (cb == 0)
+              asm volatile("" : "+v"(tt) : "v"(v0), "v"(v1));
+            else
+              asm volatile("" : "+v"(tt)
+                           : "v"(acc_c[-13]), "v"(acc_c[-9]), "v"(acc_c[-5]),
+                             "v"(acc_c[-1]));
+            rows = reinterpret_cast<const uint4*>(
+                table + ((j << (zlog + 1)) + ((long long)tt << 1)) * ROW);
+            load_block(cb + 1);
+          }
+          const uint4* r0q = rq[cb & 1][0];
+          const uint4* r1q = rq[cb & 1][1];
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            acc_c[4 * q + 0] += v0 * r0q[q].x + v1 * r1q[q].x;
+            acc_c[4 * q + 1] += v0 * r0q[q].y + v1 * r1q[q].y;
+            acc_c[4 * q + 2] += v0 * r0q[q].z + v1 * r1q[q].z;
+            acc_c[4 * q + 3] += v0 * r0q[q].w + v1 * r1q[q].w;
+          }
         }
       } else {
         u32* orow = out + (u64)key_id * (u64)n +
@@ -339,7 +416,7 @@ __global__ __launch_bounds__(256 * K) void dpf_eval_kernel(
   if constexpr (FUSED) {
     // Wave shfl reduction, then cross-wave sum through LDS.
 #pragma unroll
-    for (int w = 0; w < 16; ++w) {
+    for (int w = 0; w < ROW; ++w) {
       u32 v = acc[w];
 #pragma unroll
       for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
@@ -349,15 +426,15 @@ __global__ __launch_bounds__(256 * K) void dpf_eval_kernel(
     const int lane = t & 63, wave = t >> 6, nwaves = Z >> 6;
     if (lane == 0) {
 #pragma unroll
-      for (int w = 0; w < 16; ++w) red[wave * 16 + w] = acc[w];
+      for (int w = 0; w < ROW; ++w) red[wave * ROW + w] = acc[w];
     }
     __syncthreads();
-    if (active && t < 16) {
+    if (active && t < ROW) {  // ROW <= 64 <= Z: one thread per column
       u32 s = 0;
-      for (int wv = 0; wv < nwaves; ++wv) s += red[wv * 16 + t];
+      for (int wv = 0; wv < nwaves; ++wv) s += red[wv * ROW + t];
       // Wrapping u32 atomic add combines the 2^slog segment partials
       // exactly (mod 2^32); `out` is zeroed by the caller.
-      atomicAdd(&out[(u64)key_id * 16 + t], s);
+      atomicAdd(&out[(u64)key_id * ROW + t], s);
     }
   }
 }
@@ -393,12 +470,19 @@ int slog_for(int batch, int DS) {
 // runs and so that the tests reach every K; it is read at each launch (one
 // getenv) so a single process can compare them.  Public (dpf_hip_api.h) so
 // the tests can assert which K a launch took.
-int eval_units_per_wg(int prf, int n_units) {
+//
+// The round costs are measured for 16-word rows only.  Rows wider than that
+// allow K <= AES_MAX_UNITS_WIDE; nobody has measured their rounds, so they
+// take the largest K allowed, and a forced K is clamped to it.
+int eval_units_per_wg(int prf, int n_units, int entry_words) {
+  check_entry_words(entry_words);
   if (prf != PRF_AES128) return 1;
+  const int kmax = entry_words > 16 ? AES_MAX_UNITS_WIDE : AES_MAX_UNITS;
   if (const char* e = std::getenv("GPUDPF_AES_UNITS")) {
     const int v = std::atoi(e);
-    if (v >= 1 && v <= AES_MAX_UNITS) return v;
+    if (v >= 1 && v <= AES_MAX_UNITS) return v < kmax ? v : kmax;
   }
+  if (entry_words > 16) return kmax;
   int dev = 0, cus = 0;
   HIP_CHECK(hipGetDevice(&dev));
   HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount,
@@ -421,21 +505,25 @@ int eval_units_per_wg(int prf, int n_units) {
 namespace {
 
 // bins: nothing, or the binned kernel's device id array
-template <int PRF, bool FUSED, class... Bins>
+template <int PRF, bool FUSED, int W, class... Bins>
 void launch_eval_t(const int* keys, const u32* table, u32* out,
                    const u32* aes_tabs, int batch, long long n, int depth,
                    int zlog, hipStream_t stream, uint4* own_scratch,
                    size_t own_scratch_bytes, Bins... bins) {
-  const EvalGeom g(depth, zlog);
+  const EvalGeom g(depth, zlog, W);
   const int slog = slog_for(batch, g.DS);
   const int n_units = batch << slog;
-  const int K = eval_units_per_wg(PRF, n_units);
+  const int K = eval_units_per_wg(PRF, n_units, 16 * W);
   const size_t shmem = g.lds_bytes(PRF, K);
-  auto kern = dpf_eval_kernel<PRF, FUSED, 1, Bins...>;
+  if (shmem > 160 * 1024)
+    throw std::invalid_argument("eval launch needs more LDS than a CU has");
+  auto kern = dpf_eval_kernel<PRF, FUSED, 1, W, Bins...>;
   if constexpr (PRF == PRF_AES128) {
-    if (K == 2) kern = dpf_eval_kernel<PRF, FUSED, 2, Bins...>;
-    if (K == 3) kern = dpf_eval_kernel<PRF, FUSED, 3, Bins...>;
-    if (K == 4) kern = dpf_eval_kernel<PRF, FUSED, 4, Bins...>;
+    if (K == 2) kern = dpf_eval_kernel<PRF, FUSED, 2, W, Bins...>;
+    if constexpr (W == 1) {
+      if (K == 3) kern = dpf_eval_kernel<PRF, FUSED, 3, W, Bins...>;
+      if (K == 4) kern = dpf_eval_kernel<PRF, FUSED, 4, W, Bins...>;
+    }
   }
   allow_large_lds((const void*)kern, shmem);
   // Caller-owned scratch (launches that may overlap on different streams
@@ -464,16 +552,23 @@ void launch_eval_dispatch(std::uintptr_t keys, std::uintptr_t table,
                           std::uintptr_t out, std::uintptr_t aes_tabs,
                           int batch, long long n, int depth, int zlog, int prf,
                           std::uintptr_t stream, std::uintptr_t scratch,
-                          std::size_t scratch_bytes, Bins... bins) {
+                          std::size_t scratch_bytes, int entry_words,
+                          Bins... bins) {
+  check_entry_words(entry_words);
   if (batch <= 0) return;
   check_domain(depth, n);
   if (zlog < 6 || zlog >= depth)
     throw std::invalid_argument("zlog must be in [6, depth)");
   with_prf(prf, [&](auto P) {
-    launch_eval_t<decltype(P)::value, FUSED>(
-        as_ptr<const int>(keys), as_ptr<const u32>(table), as_ptr<u32>(out),
-        as_ptr<const u32>(aes_tabs), batch, n, depth, zlog, as_stream(stream),
-        as_ptr<uint4>(scratch), scratch_bytes, bins...);
+    auto launch = [&](auto Wc) {
+      launch_eval_t<decltype(P)::value, FUSED, decltype(Wc)::value>(
+          as_ptr<const int>(keys), as_ptr<const u32>(table), as_ptr<u32>(out),
+          as_ptr<const u32>(aes_tabs), batch, n, depth, zlog,
+          as_stream(stream), as_ptr<uint4>(scratch), scratch_bytes, bins...);
+    };
+    // only the fused kernel has wide instantiations
+    if constexpr (FUSED) with_row_blocks(entry_words, launch);
+    else launch(std::integral_constant<int, 1>{});
   });
 }
 
@@ -482,9 +577,10 @@ void launch_eval_dispatch(std::uintptr_t keys, std::uintptr_t table,
 void launch_fused(std::uintptr_t keys, std::uintptr_t table, std::uintptr_t out,
                   std::uintptr_t aes_tabs, int batch, long long n, int depth,
                   int zlog, int prf, std::uintptr_t stream,
-                  std::uintptr_t scratch, std::size_t scratch_bytes) {
+                  std::uintptr_t scratch, std::size_t scratch_bytes,
+                  int entry_words) {
   launch_eval_dispatch<true>(keys, table, out, aes_tabs, batch, n, depth, zlog,
-                             prf, stream, scratch, scratch_bytes);
+                             prf, stream, scratch, scratch_bytes, entry_words);
 }
 
 void launch_fused_binned(std::uintptr_t keys, std::uintptr_t table,
@@ -492,15 +588,18 @@ void launch_fused_binned(std::uintptr_t keys, std::uintptr_t table,
                          std::uintptr_t aes_tabs, int batch, long long n,
                          int depth, int zlog, long long num_bins, int prf,
                          std::uintptr_t stream, std::uintptr_t scratch,
-                         std::size_t scratch_bytes) {
+                         std::size_t scratch_bytes, int entry_words) {
+  check_entry_words(entry_words);
   if (num_bins < 1) throw std::invalid_argument("num_bins must be >= 1");
-  // the whole table (num_bins * n rows of 64 bytes) must be addressable
-  if (n > 0 && num_bins > (long long)(SIZE_MAX / 64) / n)
-    throw std::invalid_argument("num_bins * n * 64 bytes overflows");
+  // the whole table (num_bins * n rows of 4 * entry_words bytes) must be
+  // addressable
+  const std::size_t row_bytes = 4 * (std::size_t)entry_words;
+  if (n > 0 && num_bins > (long long)(SIZE_MAX / row_bytes) / n)
+    throw std::invalid_argument("num_bins * n * row bytes overflows");
   if (batch > 0 && bins == 0)
     throw std::invalid_argument("bins must be a device pointer");
   launch_eval_dispatch<true>(keys, table, out, aes_tabs, batch, n, depth, zlog,
-                             prf, stream, scratch, scratch_bytes,
+                             prf, stream, scratch, scratch_bytes, entry_words,
                              as_ptr<const int>(bins));
 }
 
@@ -512,7 +611,8 @@ int eval_slog(int batch, int depth, int zlog) {
 
 std::size_t eval_scratch_bytes(int batch, int depth, int zlog) {
   const int slog = eval_slog(batch, depth, zlog);  // validates the arguments
-  return EvalGeom(depth, zlog).scratch_bytes(batch << slog);
+  // the scratch does not depend on the row width
+  return EvalGeom(depth, zlog, /*W=*/1).scratch_bytes(batch << slog);
 }
 
 void launch_expand(std::uintptr_t keys, std::uintptr_t out,
@@ -520,7 +620,8 @@ void launch_expand(std::uintptr_t keys, std::uintptr_t out,
                    int zlog, int prf, std::uintptr_t stream,
                    std::uintptr_t scratch, std::size_t scratch_bytes) {
   launch_eval_dispatch<false>(keys, /*table=*/0, out, aes_tabs, batch, n, depth,
-                              zlog, prf, stream, scratch, scratch_bytes);
+                              zlog, prf, stream, scratch, scratch_bytes,
+                              /*entry_words=*/16);
 }
 
 }  // namespace gpudpf_hip

@@ -10,8 +10,11 @@ namespace gpudpf_hip {
 
 // Fused DPF expansion + table inner product (the production PIR path).
 //   keys:  device ptr, int32 [batch][524]   (wire-format keys)
-//   table: device ptr, u32 [n][16]          (leaf_perm-reordered rows)
-//   out:   device ptr, u32 [batch][16]
+//   table: device ptr, u32 [n][entry_words] (leaf_perm-reordered rows)
+//   out:   device ptr, u32 [batch][entry_words]
+//   entry_words: u32 per table row, 16, 32, 48 or 64 (anything else:
+//             std::invalid_argument before any HIP call).  A leaf's share is
+//             computed once whatever the width
 //   aes_tabs: device ptr to 5*256 u32 AES tables (only read for AES128)
 //   scratch:  0 = the shared per-device sibling-stack scratch (launches on
 //             one stream at a time); launches that may overlap on different
@@ -20,13 +23,15 @@ namespace gpudpf_hip {
 void launch_fused(std::uintptr_t keys, std::uintptr_t table, std::uintptr_t out,
                   std::uintptr_t aes_tabs, int batch, long long n, int depth,
                   int zlog, int prf, std::uintptr_t stream,
-                  std::uintptr_t scratch = 0, std::size_t scratch_bytes = 0);
+                  std::uintptr_t scratch = 0, std::size_t scratch_bytes = 0,
+                  int entry_words = 16);
+// (does not depend on entry_words)
 std::size_t eval_scratch_bytes(int batch, int depth, int zlog);
 
 // Binned variant of launch_fused (batch PIR): key i is evaluated against its
 // own bin in one launch.
-//   table: device ptr, u32 [num_bins][n][16]; every block of n = 1 << depth
-//          rows is in leaf_perm(n, zlog) order
+//   table: device ptr, u32 [num_bins][n][entry_words]; every block of
+//          n = 1 << depth rows is in leaf_perm(n, zlog) order
 //   bins:  device ptr, int32 [batch]; key i reads block bins[i].  The ids
 //          live on the device, so the launcher cannot check them: the caller
 //          guarantees 0 <= bins[i] < num_bins
@@ -36,15 +41,16 @@ void launch_fused_binned(std::uintptr_t keys, std::uintptr_t table,
                          std::uintptr_t aes_tabs, int batch, long long n,
                          int depth, int zlog, long long num_bins, int prf,
                          std::uintptr_t stream, std::uintptr_t scratch = 0,
-                         std::size_t scratch_bytes = 0);
+                         std::size_t scratch_bytes = 0, int entry_words = 16);
 
 // Launch geometry of launch_fused / launch_expand, for tests that assert
 // the regime they hit.  eval_slog: log2 of the per-key segment split
 // (j-split); pure host arithmetic, no HIP call.  eval_units_per_wg: the
 // (key, segment) units packed into one workgroup (1 unless prf is AES128);
-// honours GPUDPF_AES_UNITS and otherwise queries the current device.
+// honours GPUDPF_AES_UNITS and otherwise queries the current device.  Rows
+// wider than 16 words (entry_words as for launch_fused) take at most 2.
 int eval_slog(int batch, int depth, int zlog);
-int eval_units_per_wg(int prf, int n_units);
+int eval_units_per_wg(int prf, int n_units, int entry_words = 16);
 
 // Full expansion to low-32 one-hot shares, permuted row order
 //   out: device ptr, u32 [batch][n]  (row r = leaf_perm(idx))

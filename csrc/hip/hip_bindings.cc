@@ -63,21 +63,21 @@ PYBIND11_MODULE(_hip, m) {
         py::arg("table"), py::arg("out"), py::arg("aes_tabs"), py::arg("batch"),
         py::arg("n"), py::arg("depth"), py::arg("zlog"), py::arg("prf"),
         py::arg("stream"), py::arg("scratch") = 0,
-        py::arg("scratch_bytes") = 0,
+        py::arg("scratch_bytes") = 0, py::arg("entry_words") = 16,
         py::call_guard<py::gil_scoped_release>());
   m.def("eval_fused_binned", &gpudpf_hip::launch_fused_binned,
         py::arg("keys"), py::arg("table"), py::arg("bins"), py::arg("out"),
         py::arg("aes_tabs"), py::arg("batch"), py::arg("n"), py::arg("depth"),
         py::arg("zlog"), py::arg("num_bins"), py::arg("prf"),
         py::arg("stream"), py::arg("scratch") = 0,
-        py::arg("scratch_bytes") = 0,
+        py::arg("scratch_bytes") = 0, py::arg("entry_words") = 16,
         py::call_guard<py::gil_scoped_release>());
   m.def("eval_scratch_bytes", &gpudpf_hip::eval_scratch_bytes,
         py::arg("batch"), py::arg("depth"), py::arg("zlog"));
   m.def("eval_slog", &gpudpf_hip::eval_slog, py::arg("batch"),
         py::arg("depth"), py::arg("zlog"));
   m.def("eval_units_per_wg", &gpudpf_hip::eval_units_per_wg, py::arg("prf"),
-        py::arg("n_units"));
+        py::arg("n_units"), py::arg("entry_words") = 16);
   m.def("eval_expand", &gpudpf_hip::launch_expand, py::arg("keys"),
         py::arg("out"), py::arg("aes_tabs"), py::arg("batch"), py::arg("n"),
         py::arg("depth"), py::arg("zlog"), py::arg("prf"), py::arg("stream"),

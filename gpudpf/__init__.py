@@ -10,7 +10,8 @@ Public API parity (reference dpf.py:35-137):
     from gpudpf import DPF
     d = DPF(prf=DPF.PRF_AES128)
     k1, k2 = d.gen(k, n)
-    d.eval_init(table)          # [n, e] int32 (any n; e<=16 uses the fused path)
+    d.eval_init(table)          # [n, e] int32 (any n; e<=16 uses the fused path,
+                                # e<=64 too with DPF(fused_words=64))
     shares = d.eval_gpu([k1])   # [1, e] int32 secret shares
 """
 
@@ -19,8 +20,9 @@ try:
     from gpudpf.binned import BinnedDPF  # noqa: F401
     from gpudpf.dist import ReplicatedDPF, ShardedDPF  # noqa: F401
     from gpudpf.serving import GraphedServer  # noqa: F401
-except ImportError:
-    # Fresh checkout: the native extensions are not built yet.  Importing
+except (ImportError, AttributeError):
+    # Fresh checkout: the native extensions are not built yet (or, with
+    # AttributeError, built from an older source and due a rebuild).  Importing
     # the bare package must still work so `gpudpf._build` can bootstrap
     # (`python -m gpudpf._build` or __graft_entry__.build()).
     DPF = None  # type: ignore[assignment]

@@ -3,8 +3,8 @@
 The batch-PIR plan (pir/batch_pir.py) hashes the cold part of a table into
 `num_bins` small tables and sends `queries_per_bin` keys to every bin per
 request, so a key costs bin_size PRFs, not n.  BinnedDPF holds all bins in
-one device allocation, [num_bins, n, 16] with every block in the kernel's
-leaf_perm order, and evaluates a batch whose key i belongs to bin bins[i]
+one device allocation, [num_bins, n, 16] (rows of up to 64 words with
+fused_words, below) with every block in the kernel's leaf_perm order, and evaluates a batch whose key i belongs to bin bins[i]
 with a single launch of the binned fused kernel (csrc/hip/dpf_eval.hip).
 
 Every attribute the serving classes read keeps its meaning PER BIN
@@ -18,6 +18,10 @@ as they serve a DPF:
     k1s, k2s = d.gen_batch(rows, bins)   # key i selects rows[i] of bins[i]
     d.bind_bins(bins)                    # the fixed slot plan, uploaded once
     shares = GraphedServer(d, batch=len(bins)).eval(k1s)
+
+Bin rows wider than 16 words (a collocated plan's group_size * e) need
+BinnedDPF(fused_words=32, 48 or 64): the fused kernel then walks rows of
+that many words, still one launch and one leaf expansion per key.
 """
 
 import os
@@ -30,8 +34,8 @@ from gpudpf.dpf import DPF, _check_arg, _hip, _HAS_HIP
 
 
 class BinnedDPF(DPF):
-    def __init__(self, prf=None, device=None):
-        super().__init__(prf=prf, device=device)
+    def __init__(self, prf=None, device=None, fused_words=16):
+        super().__init__(prf=prf, device=device, fused_words=fused_words)
         self.tables = None      # natural-order bin tables (as given)
         self.bin_sizes = None   # rows of each bin
         self.num_bins = None
@@ -121,19 +125,21 @@ class BinnedDPF(DPF):
     # Server side
     # ------------------------------------------------------------------
     def bin_block(self, b):
-        """Bin b as the kernel reads it: [n, 16] int32 (CPU), zero-padded
-        to the common domain and 16 words, rows in leaf_perm(n, zlog)
-        order."""
+        """Bin b as the kernel reads it: [n, padded entry words] int32
+        (CPU), zero-padded to the common domain and a multiple of 16 words,
+        rows in leaf_perm(n, zlog) order."""
         t = self.tables[b]
-        blk = torch.zeros((self._n_domain, self.ENTRY_SIZE), dtype=torch.int32)
+        blk = torch.zeros((self._n_domain, self._entry_padded),
+                          dtype=torch.int32)
         blk[self._perm[: t.shape[0]], : t.shape[1]] = t.to(torch.int32)
         return blk
 
     def eval_init(self, tables):
         """Upload a list of [n_b, e] int32 bin tables (every n_b >= 1, one
-        e <= 16 for all).  Bins are zero-padded to the common domain
-        DPF._domain(max n_b) and each is reordered by leaf_perm; the device
-        table is [num_bins, n, 16].  The upload streams in row chunks."""
+        e <= fused_words for all).  Bins are zero-padded to the common
+        domain DPF._domain(max n_b) and each is reordered by leaf_perm; the
+        device table is [num_bins, n, e padded to 16 words].  The upload
+        streams in row chunks."""
         tables = list(tables)
         if not tables:
             raise Exception("need at least one bin table")
@@ -145,10 +151,10 @@ class BinnedDPF(DPF):
         if len(es) != 1:
             raise Exception("all bins must share one entry size (got %s)" % es)
         e = es[0]
-        if e > self.ENTRY_SIZE:
+        if e > self.fused_words:
             raise Exception("binned evaluation serves entries of at most %d "
                             "words (got %d): there is no binned two-stage path"
-                            % (self.ENTRY_SIZE, e))
+                            % (self.fused_words, e))
         self.tables = tables
         self.set_bin_sizes([t.shape[0] for t in tables])
         dev = self._setup_domain(max(self.bin_sizes), e)
@@ -173,18 +179,19 @@ class BinnedDPF(DPF):
                     t32[lo:hi].to(dev, non_blocking=False)
 
     def _launch_binned(self, keys_gpu, bins_gpu, out_gpu, scratch=None):
-        """out_gpu [b,16] += share of key i against bin bins_gpu[i]; the
-        caller zeroes it.  Metadata checks only: capture-safe."""
+        """out_gpu [b, padded entry words] += share of key i against bin
+        bins_gpu[i]; the caller zeroes it.  Metadata checks only:
+        capture-safe."""
         b = len(keys_gpu)
+        ew = self._fused_entry_words()
         stream, sptr, sbytes = self._launch_args(
-            keys_gpu, (b, self.KEY_INTS), out_gpu, (b, self.ENTRY_SIZE),
-            scratch)
+            keys_gpu, (b, self.KEY_INTS), out_gpu, (b, ew), scratch)
         _check_arg("bins", bins_gpu, self._table_gpu.device, torch.int32, (b,))
         _hip.eval_fused_binned(
             keys_gpu.data_ptr(), self._table_gpu.data_ptr(),
             bins_gpu.data_ptr(), out_gpu.data_ptr(), self._aes_ptr, b,
             self._n_domain, self._depth, self._zlog, self.num_bins,
-            self.prf_method, stream, sptr, sbytes)
+            self.prf_method, stream, sptr, sbytes, ew)
 
     def _launch_fused(self, keys_gpu, out_gpu, scratch=None):
         """As DPF._launch_fused, key i against bin plan[i] of the plan bound

@@ -58,6 +58,9 @@ class DPF(object):
     PRF_AES128 = _core.PRF_AES128
 
     ENTRY_SIZE = _core.ENTRY_WORDS  # 16 x u32 per table entry (padded)
+    MAX_FUSED_WORDS = _core.MAX_FUSED_WORDS  # widest row the fused kernel serves
+    # the row widths it serves: whole 16-word blocks up to that
+    FUSED_WIDTHS = tuple(range(ENTRY_SIZE, MAX_FUSED_WORDS + 1, ENTRY_SIZE))
     BATCH_SIZE = 512                # reference-compatible chunking constant
     MAX_LAUNCH_BATCH = 4096         # keys per kernel launch
 
@@ -71,10 +74,18 @@ class DPF(object):
         _core.PRF_AES128: "AES128",
     }
 
-    def __init__(self, prf=None, device=None):
+    def __init__(self, prf=None, device=None, fused_words=16):
+        """fused_words: the widest padded entry (16, 32, 48 or 64 words)
+        this instance serves with the fused kernel.  Wider tables take the
+        two-stage path (BinnedDPF, which has none, refuses them).  The
+        default is the 16-word kernel everywhere."""
         self.prf_method = self.DEFAULT_PRF if prf is None else prf
         self.prf_method_string = self._PRF_NAMES[self.prf_method]
         self.device = device  # resolved lazily at eval_init
+        if fused_words not in self.FUSED_WIDTHS:
+            raise Exception("fused_words must be one of %s (got %r)"
+                            % (list(self.FUSED_WIDTHS), fused_words))
+        self.fused_words = fused_words
 
         self.table = None               # natural-order table (as given)
         self.table_num_entries = None
@@ -166,6 +177,12 @@ class DPF(object):
         if self.device is None:
             self.device = "cuda:0" if torch.cuda.is_available() else "cpu"
         return torch.device(self.device)
+
+    @property
+    def fused_servable(self):
+        """Whether the fused kernel serves the set-up table: its padded
+        entries are no wider than this instance's fused_words."""
+        return self._entry_padded <= self.fused_words
 
     def _perm_rows(self, indices):
         """Permuted table rows for a tensor of natural indices (host
@@ -297,18 +314,33 @@ class DPF(object):
         touches (0 for domains whose stack fits registers + LDS)."""
         return _hip.eval_scratch_bytes(batch, self._depth, self._zlog)
 
+    def _fused_entry_words(self):
+        """Row width of a fused launch against the device table; raises on
+        a table the fused kernel does not serve (it would read the wide
+        rows as narrower ones)."""
+        if self._table_gpu is None:
+            raise Exception("table: call `eval_init` before evaluating")
+        if not self.fused_servable:
+            raise Exception(
+                "table: entries of %d words are wider than the %d this "
+                "instance serves fused (fused_words)"
+                % (self._entry_padded, self.fused_words))
+        return self._entry_padded
+
     def _launch_fused(self, keys_gpu, out_gpu, scratch=None):
-        """out_gpu [b,16] += the keys' table shares; the caller zeroes it
-        (the j-split segments accumulate with atomics).  Launches that can
-        be in flight together each need their own `scratch`."""
+        """out_gpu [b, padded entry words] += the keys' table shares; the
+        caller zeroes it (the j-split segments accumulate with atomics).
+        Launches that can be in flight together each need their own
+        `scratch`."""
         b = len(keys_gpu)
+        ew = self._fused_entry_words()
         stream, sptr, sbytes = self._launch_args(
-            keys_gpu, (b, self.KEY_INTS), out_gpu, (b, self.ENTRY_SIZE),
-            scratch)
+            keys_gpu, (b, self.KEY_INTS), out_gpu, (b, ew), scratch)
         _hip.eval_fused(
             keys_gpu.data_ptr(), self._table_gpu.data_ptr(),
             out_gpu.data_ptr(), self._aes_ptr, b, self._n_domain,
-            self._depth, self._zlog, self.prf_method, stream, sptr, sbytes)
+            self._depth, self._zlog, self.prf_method, stream, sptr, sbytes,
+            ew)
 
     def _launch_expand(self, keys_gpu, shares_gpu, scratch=None):
         """shares_gpu [b,n] = one-hot shares, rows in leaf_perm order."""
@@ -354,8 +386,9 @@ class DPF(object):
         strategy: "fused" (production: expansion fused with the table MAC)
         or "two_stage" (expand one-hot shares, then multiply against the
         table on the MFMA matrix cores — the runtime strategy selection the
-        reference leaves as a TODO, dpf.py:26).  Entries wider than 16
-        words route through "two_stage" automatically."""
+        reference leaves as a TODO, dpf.py:26).  Entries wider than
+        fused_words (16 by default) route through "two_stage"
+        automatically; "coop" serves 16-word tables only."""
         if self._table_gpu is None:
             raise Exception("Must call `eval_init` before `eval_gpu`")
         if not _HAS_HIP:
@@ -367,12 +400,15 @@ class DPF(object):
                 % (n, self._n_domain)
             )
         keys_gpu = kt.to(self._table_gpu.device, non_blocking=True)
-        if self._entry_padded > self.ENTRY_SIZE and not one_hot_only:
+        if not self.fused_servable and not one_hot_only:
             strategy = "two_stage"  # wide entries go through the MFMA path
         if strategy == "two_stage" and not one_hot_only:
             res = self._eval_gpu_two_stage(keys_gpu)
         else:
             if strategy == "coop":
+                if self._entry_padded > self.ENTRY_SIZE and not one_hot_only:
+                    raise Exception("the coop strategy serves tables of at "
+                                    "most %d words" % self.ENTRY_SIZE)
                 run = partial(self._eval_coop, fused=not one_hot_only)
             elif one_hot_only:
                 run = partial(self._eval_one_hot, bfs=strategy == "bfs")
@@ -388,11 +424,12 @@ class DPF(object):
 
     def _new_out(self, b, one_hot):
         """[b, n] uninitialized (one-hot kernels write every word) or
-        [b, 16] zeroed (fused kernels accumulate with atomics)."""
+        [b, padded entry words] zeroed (fused kernels accumulate with
+        atomics; raises on a table the fused kernel does not serve)."""
         if one_hot:
             return torch.empty((b, self._n_domain), dtype=torch.int32,
                                device=self._table_gpu.device)
-        return torch.zeros((b, self.ENTRY_SIZE), dtype=torch.int32,
+        return torch.zeros((b, self._fused_entry_words()), dtype=torch.int32,
                            device=self._table_gpu.device)
 
     def _eval_fused(self, keys_gpu):
@@ -480,8 +517,9 @@ class DPF(object):
 
     def eval_gpu_into(self, keys_gpu, out_gpu):
         """Zero-copy serving path: keys already on device as [b,524] int32,
-        fused result written into out_gpu [b,16] int32 asynchronously on the
-        current stream (no host sync)."""
+        fused result written into out_gpu [b, padded entry words] int32
+        ([b,16] by default) asynchronously on the current stream (no host
+        sync)."""
         if os.environ.get("GPUDPF_DEBUG"):
             # optional (synchronizing) domain check for the serving path
             _kt, n, _d = self._keys_tensor(keys_gpu)

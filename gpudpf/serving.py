@@ -8,7 +8,8 @@ idiomatic MI355X replacement for the reference's per-call stream
 creation (dpf_wrapper.cu:155-156).
 
 Serves all backend shapes:
-  * fused (entry <= 16 words): one captured zero+fused launch;
+  * fused (entry <= 16 words, or <= the DPF's fused_words): one captured
+    zero+fused launch;
   * wide entries: captured expand + streaming-GEMM sequence (the MFMA
     digit-plane path allocates per call and is not graph-capturable;
     the streaming GEMM reads the table in place, so the whole two-stage
@@ -137,10 +138,10 @@ class GraphedServer:
         self.device = _table_device(dpf)
         self.dpf = dpf
         self.batch = batch
-        self.wide = dpf._entry_padded > DPF.ENTRY_SIZE
+        self.wide = not dpf.fused_servable
         if self.sharded is not None and self.wide:
             raise Exception("sharded GraphedServer serves the fused path "
-                            "(entry <= 16 words)")
+                            "(entry <= %d words)" % dpf.fused_words)
         if self.wide:
             shares_bytes = batch * dpf._n_domain * 4
             if shares_bytes > self.MAX_WIDE_SHARES_BYTES:
@@ -197,9 +198,9 @@ class PipelinedServer:
 
     def __init__(self, dpf: DPF, batch: int, depth: int = 2):
         self.device = _table_device(dpf)
-        if dpf._entry_padded != DPF.ENTRY_SIZE:
+        if not dpf.fused_servable:
             raise Exception("PipelinedServer serves the fused path "
-                            "(entry <= 16 words)")
+                            "(entry <= %d words)" % dpf.fused_words)
         self.dpf = dpf
         self.batch = batch
         self.depth = depth
@@ -257,9 +258,10 @@ class TwoStageServer:
 
     def __init__(self, dpf: DPF, batch: int, depth: int = 2):
         dev = self.device = _table_device(dpf)
-        if dpf._entry_padded <= DPF.ENTRY_SIZE:
+        if dpf.fused_servable:
             raise Exception("TwoStageServer serves wide entries "
-                            "(> 16 words); use PipelinedServer")
+                            "(> %d words); use PipelinedServer"
+                            % dpf.fused_words)
         if batch > 16:
             raise Exception("streaming-GEMM batch is capped at 16 per "
                             "table pass; lower the batch")

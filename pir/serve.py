@@ -13,6 +13,12 @@ answers:
     a, b = server1(k1s), server2(k2s)         # [slots, group_size * e] each
     rows = decode(opt, meaning, a, b, e)      # {cold entry: its row}
 
+A collocated plan's rows are group_size * e words.  Beyond 16 words pass the
+width limit on both sides (at most 64):
+
+    tables = bin_tables(opt, table, max_words=64)
+    dpf = BinnedDPF(fused_words=64)
+
 Every request issues num_bins * queries_per_bin keys in the same slot
 order whatever it asks for, so the servers learn nothing from which bins
 were needed.
@@ -22,7 +28,7 @@ import collections
 
 import torch
 
-ENTRY_WORDS = 16  # widest row the fused (binned) kernel serves
+ENTRY_WORDS = 16  # widest row a default BinnedDPF (fused_words=16) serves
 
 
 def _group_size(opt):
@@ -34,16 +40,17 @@ def _bin_groups(opt, b):
     return sorted(opt.bins.get(b, []))
 
 
-def bin_tables(opt, table):
+def bin_tables(opt, table, max_words=ENTRY_WORDS):
     """The per-bin tables of plan `opt` over `table` ([num_entries, e]
     int32): row r of bin b is the concatenation of the rows of the entries
     of group sorted(opt.bins[b])[r], zero-padded to group_size * e words.
-    A bin the hash left empty gets one zero row, so every bin exists."""
+    A bin the hash left empty gets one zero row, so every bin exists.
+    max_words is the fused_words of the BinnedDPF that will serve them."""
     e = int(table.shape[1])
     width = _group_size(opt) * e
-    if width > ENTRY_WORDS:
+    if width > max_words:
         raise Exception("group_size * e = %d words, but a binned row holds "
-                        "at most %d" % (width, ENTRY_WORDS))
+                        "at most %d" % (width, max_words))
     t32 = table.to(torch.int32)
     out = []
     for b in range(opt.pir.num_bins):
