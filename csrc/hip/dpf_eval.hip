@@ -25,14 +25,18 @@
 //     traffic than the reference's mod-2^128 MAC (dpf_hybrid.cu:166-172),
 //     with bit-identical output.  Table loads are issued BEFORE the leaf
 //     PRFs of the same step, so ~1000 cycles of cipher work hides them.
-//   * AES T-table: a single 256-entry table replicated 64-way (byte
-//     entry*256 + (lane%64)*4, at LDS byte 0) so every lane reads its own
-//     LDS bank — measured 4.3x bank-conflict amplification with flat
-//     tables (SQ_LDS_BANK_CONFLICT 3.5e10 vs SQ_INSTS_LDS 8.1e9,
-//     profiles/) — and a lookup address is one v_perm_b32 of a state word.
-//     te1..te3 are byte rotations of te0 (1 v_alignbit per lookup) and
-//     sbox[x] = byte2 of te0[x], so one table serves the whole cipher;
-//     the five-term round sums are two 3-input xors (v_bitop3_b32).
+//   * AES T-table: 256 rows of 256 bytes at LDS byte 0, each holding 32
+//     copies of te0[entry] and 32 of te2[entry] = ror16(te0[entry]) (byte
+//     entry*256 + half*128 + (lane%32)*4).  A ds_read_b32 is served in two
+//     groups of 32 lanes, so inside a group every lane reads its own LDS
+//     bank — measured 4.3x bank-conflict amplification with flat tables
+//     (SQ_LDS_BANK_CONFLICT 3.5e10 vs SQ_INSTS_LDS 8.1e9, profiles/) — a
+//     lookup address is one v_perm_b32 of a state word, and the te2 word
+//     is the same address read with the immediate offset:128.  Rotation
+//     commutes with xor, so a MixColumns word is
+//     xor3(te0, te2, ror8(xor3(te0, te2, rol8(k)))): two v_bitop3_b32 and
+//     ONE v_alignbit_b32, and the key schedule runs on rol8(k) throughout.
+//     sbox[x] = byte 2 of te0[x], so the table serves the whole cipher.
 //   * Table layout: row(idx) = j<<(zlog+1) | t<<1 | b (leaf_perm in
 //     csrc/core/dpf_core.cc): at DFS step j the workgroup reads one
 //     contiguous 32 KB slab; every lane reads its two rows as 8 contiguous
@@ -69,7 +73,7 @@ constexpr int MAX_LDS_LEVELS = 4;
 // Most (key, segment) units one AES workgroup walks (they share the table)
 constexpr int AES_MAX_UNITS = 4;
 // The same for rows wider than 16 words.  The K = 4 kernel lives in 128
-// VGPRs and uses 127 of them at 16 words, so it has no room for the 16*W
+// VGPRs and uses all of them at 16 words, so it has no room for the 16*W
 // accumulators of a wide row; at K <= 2 a workgroup is at most 8 waves and
 // a wave may take 256.
 constexpr int AES_MAX_UNITS_WIDE = 2;
@@ -167,7 +171,7 @@ __device__ __forceinline__ void expand_pair(uint4 seed, int i,
 // ---------------------------------------------------------------------------
 // Main kernel.  A UNIT is Z threads walking one (key, segment) pair; a
 // workgroup holds K units (K = 1 except for AES, where the K units share
-// one 64 KiB te0 table so the table does not cost occupancy).  Dynamic LDS
+// one 64 KiB te0/te2 table so the table does not cost occupancy).  Dynamic LDS
 // map (the kernel has no static LDS, so it starts at LDS byte 0):
 //   [aes: 0/16384 u32] then K unit slices of
 //   [cw: 128 uint4][shared: Z*max(2, min(DS-3, 4)) uint4][red: Z/64*16*W u32]
@@ -243,7 +247,7 @@ __global__ __launch_bounds__(256 * K) void dpf_eval_kernel(
   u32* red = reinterpret_cast<u32*>(shared_region + g.shared_u4);
   uint4* gstack = scratch + g.scratch_u4(unit);
 
-  // Stage codewords per unit; the AES te0 table once per workgroup.
+  // Stage codewords per unit; the AES te0/te2 table once per workgroup.
   if (active) {
     for (int idx = t; idx < 2 * kCwPerSel; idx += Z)
       cw_lds[idx] =
@@ -463,7 +467,9 @@ int slog_for(int batch, int DS) {
 // launch takes ceil(workgroups / CUs) rounds of K units each.  A round gets
 // cheaper per unit as K adds waves per SIMD, but not in proportion:
 // measured at n = 2^20, batch 512 on MI355X (profiles/PROFILING.md) a
-// round of 1/2/3/4 units takes 3.6/4.6/5.2/7.5 ms.  Take the K with the
+// round of 1/2/3/4 units took 3.6/4.6/5.2/7.5 ms (2.9/3.7/4.5/6.4 ms since
+// the te0/te2 table rows: nearly the same ratios, so round_cost keeps the
+// first set and no choice changes).  Take the K with the
 // cheapest rounds x cost, the smallest on ties: 2048 units -> K = 4 (2
 // rounds on 256 CUs); 1200 units -> K = 3; a single key's 256 segments ->
 // K = 1 (one unit on every CU).  GPUDPF_AES_UNITS=1..4 forces K, for A/B

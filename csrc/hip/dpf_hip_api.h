@@ -97,6 +97,12 @@ void launch_probe_prf(std::uintptr_t seeds, std::uintptr_t aes_tabs,
                       std::uintptr_t single0, std::uintptr_t single1,
                       std::uintptr_t low0, std::uintptr_t low1, int count,
                       int prf, std::uintptr_t stream);
+// The AES table as the kernels stage it in LDS (prf_device.h), copied out by
+// one workgroup of `threads` threads (a multiple of 64 up to 1024).
+//   out: device ptr, u32 [16384]: word e*64 + h*32 + c is te0[e] (h = 0) or
+//        te2[e] (h = 1) for every copy c
+void launch_probe_aes_lds(std::uintptr_t aes_tabs, std::uintptr_t out,
+                          int threads, std::uintptr_t stream);
 
 // The three GEMMs.  Each splits K into `segs` slices of `kchunk` rows
 // (KSplit and the shared arithmetic: hip_util.h), and each *_split query is

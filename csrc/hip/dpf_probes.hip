@@ -1,5 +1,6 @@
 // Measurement and unit-test probes of the device PRFs (prf_device.h): the
-// PRF speed-of-light microbenchmark and the ALU / PRF probe kernels.
+// PRF speed-of-light microbenchmark, the ALU / PRF probe kernels and the
+// probe of the staged AES table.
 
 #include <hip/hip_runtime.h>
 
@@ -92,6 +93,32 @@ __global__ __launch_bounds__(256) void probe_prf_kernel(
   prf_pair_low<PRF>(s, T, l0, l1);
   low0[i] = l0;
   low1[i] = l1;
+}
+
+// The AES table as aes_lds_init stages it: one workgroup of `threads`
+// threads stages and copies the AES_LDS_WORDS words out unchanged.  The
+// staging loop strides by the workgroup size, so tests/
+// test_gpu_aes_lds_layout.py runs it at every size the eval kernel uses.
+__global__ __launch_bounds__(1024) void probe_aes_lds_kernel(
+    const u32* __restrict__ aes_tabs, u32* __restrict__ out) {
+  extern __shared__ u32 smem[];
+  aes_lds_init<PRF_AES128>(smem, aes_tabs);
+  for (int idx = (int)threadIdx.x; idx < AES_LDS_WORDS; idx += (int)blockDim.x)
+    out[idx] = smem[idx];
+}
+
+void launch_probe_aes_lds(std::uintptr_t aes_tabs, std::uintptr_t out,
+                          int threads, std::uintptr_t stream) {
+  if (threads < 64 || threads > 1024 || threads % 64 != 0)
+    throw std::invalid_argument(
+        "probe_aes_lds: threads must be a multiple of 64 in [64, 1024]");
+  check_ptrs("probe_aes_lds", {aes_tabs, out});
+  const size_t shmem = aes_lds_u32(PRF_AES128) * sizeof(u32);
+  allow_large_lds((const void*)probe_aes_lds_kernel, shmem);
+  hipLaunchKernelGGL(probe_aes_lds_kernel, dim3(1), dim3(threads), shmem,
+                     as_stream(stream), as_ptr<const u32>(aes_tabs),
+                     as_ptr<u32>(out));
+  HIP_CHECK(hipGetLastError());
 }
 
 void launch_probe_alu(std::uintptr_t a, std::uintptr_t b,

@@ -127,6 +127,9 @@ PYBIND11_MODULE(_hip, m) {
         py::arg("single0"), py::arg("single1"), py::arg("low0"),
         py::arg("low1"), py::arg("count"), py::arg("prf"), py::arg("stream"),
         py::call_guard<py::gil_scoped_release>());
+  m.def("probe_aes_lds", &gpudpf_hip::launch_probe_aes_lds,
+        py::arg("aes_tabs"), py::arg("out"), py::arg("threads"),
+        py::arg("stream"), py::call_guard<py::gil_scoped_release>());
   m.def("ensure_aes_tables", &ensure_aes_tables, py::arg("device"));
   m.def("device_count", &device_count);
 }

@@ -4,7 +4,7 @@
 // against the CPU core).
 //
 // CONTRACT for kernels that build an AesLds (see the AES section below):
-// no static LDS, and the replicated te0 table (aes_stage_table) first in
+// no static LDS, and the replicated te0/te2 table (aes_stage_table) first in
 // the dynamic LDS map, so that the table starts at LDS byte 0.
 //
 // How the file is organised, and how a change to it is checked for equal
@@ -29,8 +29,6 @@ __device__ __forceinline__ u32 rotl(u32 v, int s) {
   return (v << s) | (v >> (32 - s));  // lowers to v_alignbit_b32
 }
 __device__ __forceinline__ u32 rotr8(u32 v) { return (v >> 8) | (v << 24); }
-__device__ __forceinline__ u32 rotr16(u32 v) { return (v >> 16) | (v << 16); }
-__device__ __forceinline__ u32 rotr24(u32 v) { return (v >> 24) | (v << 8); }
 
 // The unpacked root seed of the key that starts at `key` (wire layout in
 // dpf_core.h)
@@ -233,29 +231,48 @@ __device__ __forceinline__ void chacha12_pair_low_core(uint4 seed, u32& lo0,
 }
 
 // ---------------------------------------------------------------------------
-// AES-128, replicated-LDS variant (fused kernel).  The LDS holds te0
-// replicated AES_REP = 64-way with a 256-byte entry stride: word (entry e,
-// copy c) sits at LDS byte e*256 + c*4, and lane l always uses copy l%64.
-//   * Bank = (addr/4)%32 = l%32 inside each 32-lane ds_read_b32 group:
-//     conflict-free.
+// AES-128, replicated-LDS variant (fused kernel).  The LDS holds te0 and
+// te2 = ror16(te0), each replicated AES_COPIES = 32-way, with a 256-byte
+// entry stride: the word (entry e, copy c, half h) sits at LDS byte
+// e*256 + h*128 + c*4, half 0 = te0[e], half 1 = te2[e], and lane l always
+// uses copy l%32.
+//   * Bank = (addr/4)%32 = (e*64 + h*32 + c)%32 = c.  A ds_read_b32 is
+//     served in two groups of 32 lanes, {0-31} and {32-63}; inside a group
+//     every lane has its own copy, hence its own bank: conflict-free.
+//     Lanes l and l+32 share a copy but are never in the same group.
 //   * The byte address of te0[byte K of w] is ONE v_perm_b32: byte 1 of
-//     the address is byte K of w, byte 0 is lane*4 (<= 252), bytes 2..3
-//     are zero.  (The 32-way layout needed bfe + shift-add + add.)
+//     the address is byte K of w, byte 0 is (lane%32)*4 (<= 124), bytes
+//     2..3 are zero.  te2[byte K of w] is the SAME address read at +128,
+//     which is the ds_read_b32 immediate `offset:128`: no VALU
+//     instruction, no second address register.
 //   * The table starts at LDS byte 0, so that integer IS the address: the
 //     access is formed as an address_space(3) load from it, with no add
 //     of a table base.  This relies on every kernel that builds an AesLds
 //     having no static LDS (dynamic LDS then starts at 0) and placing the
 //     table first in its dynamic LDS map.
 //   te0[x] bytes (MSB..LSB) = [2s, s, s, 3s];  te1 = ror8(te0),
-//   te2 = ror16, te3 = ror24;  sbox[x] = byte2 of te0[x].
+//   te2 = ror16, te3 = ror24;  sbox[x] = byte 2 of te0[x] = byte 0 of
+//   te2[x].
 //
-// Everything that contract fixes is stated here: the table's size
+// Rotations.  Rotation commutes with xor, so a MixColumns word
+//   te0[a] ^ ror8(te0[b]) ^ ror16(te0[c]) ^ ror24(te0[d]) ^ k
+// is  xor3(te0[a], te2[c], ror8(xor3(te0[b], te2[d], rol8(k)))):  one
+// rotate per word (AesLds::mix).  The key schedule is equivariant under
+// byte rotation (RotWord and SubWord act bytewise; only the round constant
+// moves, from byte 3 to byte 0), so aes_cipher_pair runs it on
+// q = rol8(k) from the start and never forms k: the last round's sbox
+// gather places its bytes one position up as well, and the rotation that
+// is left folds into the byte swap at the cipher's exit (bswap_rol8).
+//
+// Everything the contract fixes is stated here: the table's size
 // (aes_lds_u32: what a launcher adds to its dynamic LDS and a kernel skips
 // to reach its own LDS), its staging (aes_stage_table) and the lane's
 // binding (AesLds::lane); aes_lds_init is the three together.
 // ---------------------------------------------------------------------------
-constexpr int AES_REP = 64;
+constexpr int AES_COPIES = 32;            // one per lane of a ds_read_b32 group
+constexpr int AES_REP = AES_COPIES * 2;   // words per entry: 32 te0, 32 te2
 constexpr int AES_LDS_WORDS = 256 * AES_REP;  // 64 KiB
+constexpr u32 AES_TE2_BYTES = AES_COPIES * 4;  // te2 half: +128 in the row
 
 // u32s of dynamic LDS the table takes in front of a kernel's own LDS map
 __host__ __device__ constexpr int aes_lds_u32(int prf) {
@@ -266,25 +283,40 @@ __device__ __forceinline__ u32 xor3(u32 a, u32 b, u32 c) {
   return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96);  // a ^ b ^ c
 }
 
-// [S(a) S(b) S(c) S(d)] (MSB..LSB) from the four te0 words of a..d: sbox
-// is byte 2 of te0, gathered by two v_perm_b32 with disjoint bytes (the
-// caller xors the halves into its sum).
-__device__ __forceinline__ u32 aes_sb_hi(u32 ta, u32 tb) {
-  return __builtin_amdgcn_perm(ta, tb, 0x06020c0cu);
+// Two sbox bytes gathered into one word by a v_perm_b32: byte BA of `ta`
+// goes to result byte PA, byte BB of `tb` to result byte PB, the other two
+// bytes are zero.  sbox is byte 2 of a te0 word and byte 0 of a te2 word.
+// Two gathers with disjoint bytes make a SubWord; the caller's three-input
+// xor folds them into its sum.
+template <int PA, int PB, int BA = 2, int BB = 2>
+__device__ __forceinline__ u32 aes_sb_pair(u32 ta, u32 tb) {
+  static_assert(PA != PB, "the two bytes land in different places");
+  constexpr u32 sel = (0x0c0c0c0cu & ~(0xffu << (8 * PA)) &
+                       ~(0xffu << (8 * PB))) |
+                      ((4u + BA) << (8 * PA)) | ((u32)BB << (8 * PB));
+  return __builtin_amdgcn_perm(ta, tb, sel);
 }
-__device__ __forceinline__ u32 aes_sb_lo(u32 tc, u32 td) {
-  return __builtin_amdgcn_perm(tc, td, 0x0c0c0602u);
+
+// rol8(bswap32(x)) = bswap32(ror8(x)): between the little-endian seed /
+// output words and the cipher's byte-rotated big-endian words, one v_perm_b32
+__device__ __forceinline__ u32 bswap_rol8(u32 x) {
+  return __builtin_amdgcn_perm(0u, x, 0x01020300u);
 }
 
 struct AesLds {
-  u32 lane4;  // (threadIdx.x % 64) * 4
+  u32 lane4;  // (threadIdx.x % 32) * 4
   // The calling lane's copy of the table
   static __device__ __forceinline__ AesLds lane() {
-    return AesLds{((u32)threadIdx.x & 63u) << 2};
+    return AesLds{((u32)threadIdx.x & (u32)(AES_COPIES - 1)) << 2};
   }
   typedef __attribute__((address_space(3))) const u32 lds_u32;
   static __device__ __forceinline__ u32 ld(u32 byte_addr) {
     return *reinterpret_cast<lds_u32*>(byte_addr);
+  }
+  // the te2 word of the row whose te0 word is at byte_addr: the constant
+  // becomes the read's immediate offset
+  static __device__ __forceinline__ u32 ld_te2(u32 byte_addr) {
+    return reinterpret_cast<lds_u32*>(byte_addr)[AES_TE2_BYTES / 4];
   }
   // byte address of te0[byte K of w] (K = 0 is the LSB)
   template <int K>
@@ -293,30 +325,54 @@ struct AesLds {
   }
   template <int K>
   __device__ __forceinline__ u32 te0_b(u32 w) const { return ld(addr_b<K>(w)); }
-  // One MixColumns output word: te0[a.b3] ^ te1[b.b2] ^ te2[c.b1] ^
-  // te3[d.b0] ^ k as two 3-input xors.
-  __device__ __forceinline__ u32 col(u32 a, u32 b, u32 c, u32 d, u32 k) const {
-    return xor3(xor3(te0_b<3>(a), rotr8(te0_b<2>(b)), rotr16(te0_b<1>(c))),
-                rotr24(te0_b<0>(d)), k);
+  template <int K>
+  __device__ __forceinline__ u32 te2_b(u32 w) const {
+    return ld_te2(addr_b<K>(w));
   }
-  // One last-round output word: [S(a.b3) S(b.b2) S(c.b1) S(d.b0)] ^ k
-  __device__ __forceinline__ u32 last(u32 a, u32 b, u32 c, u32 d, u32 k) const {
-    return xor3(aes_sb_hi(te0_b<3>(a), te0_b<2>(b)),
-                aes_sb_lo(te0_b<1>(c), te0_b<0>(d)), k);
+  // The same three for byte K of the word k given as q = rol8(k): byte
+  // (K+1)%4 of q
+  template <int K>
+  __device__ __forceinline__ u32 addr_kb(u32 q) const {
+    return addr_b<(K + 1) & 3>(q);
+  }
+  template <int K>
+  __device__ __forceinline__ u32 te0_kb(u32 q) const { return ld(addr_kb<K>(q)); }
+  template <int K>
+  __device__ __forceinline__ u32 te2_kb(u32 q) const {
+    return ld_te2(addr_kb<K>(q));
+  }
+  // te0a ^ ror8(te0b) ^ te2c ^ ror8(te2d) ^ ror8(q) from four looked-up
+  // words and q = rol8(round key word)
+  static __device__ __forceinline__ u32 mix(u32 te0a, u32 te0b, u32 te2c,
+                                            u32 te2d, u32 q) {
+    return xor3(te0a, te2c, rotr8(xor3(te0b, te2d, q)));
+  }
+  // One MixColumns output word: te0[a.b3] ^ te1[b.b2] ^ te2[c.b1] ^
+  // te3[d.b0] ^ k, given q = rol8(k)
+  __device__ __forceinline__ u32 col(u32 a, u32 b, u32 c, u32 d, u32 q) const {
+    return mix(te0_b<3>(a), te0_b<2>(b), te2_b<1>(c), te2_b<0>(d), q);
+  }
+  // One last-round output word, rotated like its key word:
+  // rol8([S(a.b3) S(b.b2) S(c.b1) S(d.b0)] ^ k), given q = rol8(k)
+  __device__ __forceinline__ u32 last(u32 a, u32 b, u32 c, u32 d, u32 q) const {
+    return xor3(aes_sb_pair<0, 3>(te0_b<3>(a), te0_b<2>(b)),
+                aes_sb_pair<2, 1>(te0_b<1>(c), te0_b<0>(d)), q);
   }
 };
 
-// Stage the replicated te0 table at LDS byte 0 (all threads of the
-// workgroup; the caller synchronizes); nothing for the other PRFs.  `lds0`
-// must be the start of the kernel's dynamic LDS.  Word index e*64 + c =>
-// consecutive threads write consecutive banks.
+// Stage the table at LDS byte 0 (all threads of the workgroup; the caller
+// synchronizes); nothing for the other PRFs.  `lds0` must be the start of
+// the kernel's dynamic LDS.  Word index e*64 + h*32 + c => consecutive
+// threads write consecutive banks, and a wave writes one whole row: lanes
+// 0-31 its te0 half, lanes 32-63 its te2 half.
 template <int PRF>
 __device__ __forceinline__ void aes_stage_table(
     u32* lds0, const u32* __restrict__ aes_tabs) {
   if constexpr (PRF == PRF_AES128) {
+    // global layout: te0 at word 0, te2 at word 512
     for (int idx = (int)threadIdx.x; idx < AES_LDS_WORDS;
          idx += (int)blockDim.x)
-      lds0[idx] = aes_tabs[idx >> 6];  // global layout: te0 at offset 0
+      lds0[idx] = aes_tabs[(((idx >> 5) & 1) << 9) + (idx >> 6)];
   }
 }
 
@@ -339,71 +395,80 @@ __device__ __forceinline__ AesLds aes_lds_init(
 template <bool LOW>
 __device__ __forceinline__ void aes_cipher_pair(uint4 seed, const AesLds& T,
                                                 uint4& ra, uint4& rb) {
-  u32 k0 = __builtin_bswap32(seed.x), k1 = __builtin_bswap32(seed.y),
-      k2 = __builtin_bswap32(seed.z), k3 = __builtin_bswap32(seed.w);
-  u32 s0 = k0, s1 = k1, s2 = k2, s3 = k3;
-  u32 u0 = (1u << 24) ^ k0, u1 = k1, u2 = k2, u3 = k3;
-  u32 rcon = 0x01u;
-  // next round key (k0..k3 = rk[4r-4..4r-1] become rk[4r..4r+3])
+  // The schedule runs on q = rol8(round key) throughout (header comment:
+  // Rotations).  Before round 1 the state is the key itself, so q0..q3 are
+  // also the state, read through the *_kb accessors.
+  u32 q0 = bswap_rol8(seed.x), q1 = bswap_rol8(seed.y),
+      q2 = bswap_rol8(seed.z), q3 = bswap_rol8(seed.w);
+  u32 rcon = 0x02u;
+  // next round key (q0..q3 = rol8 of rk[4r-4..4r-1] become those of
+  // rk[4r..4r+3]): SubWord(RotWord(.)) reads q3 as it would read k3, and
+  // the round constant sits in byte 0
   auto next_round_key = [&] {
-    k0 = xor3(aes_sb_hi(T.te0_b<2>(k3), T.te0_b<1>(k3)),
-              aes_sb_lo(T.te0_b<0>(k3), T.te0_b<3>(k3)), k0) ^ (rcon << 24);
+    q0 = xor3(aes_sb_pair<3, 2>(T.te0_b<2>(q3), T.te0_b<1>(q3)),
+              aes_sb_pair<1, 0>(T.te0_b<0>(q3), T.te0_b<3>(q3)), q0) ^ rcon;
     rcon = (rcon << 1) ^ ((rcon & 0x80u) ? 0x11bu : 0u);
     rcon &= 0xffu;
-    k1 ^= k0; k2 ^= k1; k3 ^= k2;
+    q1 ^= q0; q2 ^= q1; q3 ^= q2;
   };
-  int r_begin = 1;
+  // Round 1.  The two children's plaintexts (pos 0 / pos 1) differ in a
+  // single byte, so their states agree except for byte 3 of word 0: the 16
+  // lookups x<word><byte> below are both children's, and child b costs ONE
+  // more (x03b).  Bytes 3 and 2 of a word are read from te0, bytes 1 and 0
+  // from te2, as AesLds::col does.
+  const u32 a0 = T.addr_kb<3>(q0);
+  const u32 x03 = AesLds::ld(a0), x02 = T.te0_kb<2>(q0),
+            x01 = T.te2_kb<1>(q0), x00 = T.te2_kb<0>(q0);
+  const u32 x13 = T.te0_kb<3>(q1), x12 = T.te0_kb<2>(q1),
+            x11 = T.te2_kb<1>(q1), x10 = T.te2_kb<0>(q1);
+  const u32 x23 = T.te0_kb<3>(q2), x22 = T.te0_kb<2>(q2),
+            x21 = T.te2_kb<1>(q2), x20 = T.te2_kb<0>(q2);
+  const u32 x33 = T.te0_kb<3>(q3), x32 = T.te0_kb<2>(q3),
+            x31 = T.te2_kb<1>(q3), x30 = T.te2_kb<0>(q3);
+  // bit 0 of that byte flips: entry index ^ 1 is address ^ 256
+  const u32 x03b = AesLds::ld(a0 ^ 256u);
+  // Round 1's key.  Word 3 of the state is the key word k3 (the position
+  // byte only enters word 0), so x33..x30 also carry the sbox bytes of the
+  // round-1 key schedule (byte 2 of a te0 word, byte 0 of a te2 word): no
+  // separate sbox lookups, hence no next_round_key.
+  // rol8([S(b2) S(b1) S(b0) S(b3)]) = [S(b1) S(b0) S(b3) S(b2)] of k3
+  q0 = xor3(aes_sb_pair<3, 2, 0, 0>(x31, x30), aes_sb_pair<1, 0>(x33, x32),
+            q0) ^ 0x01u;
+  q1 ^= q0; q2 ^= q1; q3 ^= q2;
+  u32 s0 = AesLds::mix(x03, x12, x21, x30, q0);
+  u32 s1 = AesLds::mix(x13, x22, x31, x00, q1);
+  u32 s2 = AesLds::mix(x23, x32, x01, x10, q2);
+  u32 s3 = AesLds::mix(x33, x02, x11, x20, q3);
+  // the un-rotated te0 term is the one that differs
+  u32 u0 = xor3(s0, x03, x03b), u1 = s1, u2 = s2, u3 = s3;
+  int r_begin = 2;
 #ifndef GPUDPF_AES_NOSHARE
-  // Shared-prefix rounds: the two children's plaintexts (pos 0 / pos 1)
-  // differ in a single byte, so their states agree except for byte
-  // (s0 >> 24) until MixColumns diffuses it — round 1 of child b costs
-  // ONE extra T-lookup (all four output words share), and round 2 shares
-  // 12 of its 16 lookups (each output word reads exactly one byte of the
-  // diverged word 0).  Saves ~27 of ~320 lookups per pair; rounds 3+ are
-  // fully diverged and run the common loop below.  A/B toggle:
-  // compile with -DGPUDPF_AES_NOSHARE for the straight dual-cipher
-  // variant (measured comparison in profiles/PROFILING.md).
+  // Shared round 2: the states still agree in words 1..3, and each output
+  // word reads exactly one byte of the diverged word 0, so round 2 shares
+  // 12 of its 16 lookups.  With round 1 that saves ~27 of ~320 lookups per
+  // pair; rounds 3+ are fully diverged and run the common loop below.
+  // A/B toggle: compile with -DGPUDPF_AES_NOSHARE to run round 2 in the
+  // common loop as well (measured comparison in profiles/PROFILING.md).
   {
-    // round 1.  s3 == k3 here (the position byte only enters s0), so the
-    // four te0 words of s3 the cipher round reads anyway also carry the
-    // sbox bytes of the round-1 key schedule: no separate sbox lookups,
-    // hence no next_round_key.
-    const u32 t33 = T.te0_b<3>(s3), t32 = T.te0_b<2>(s3),
-              t31 = T.te0_b<1>(s3), t30 = T.te0_b<0>(s3);
-    k0 = xor3(aes_sb_hi(t32, t31), aes_sb_lo(t30, t33), k0) ^ (rcon << 24);
-    rcon = 0x02u;
-    k1 ^= k0; k2 ^= k1; k3 ^= k2;
-    const u32 a0 = T.addr_b<3>(s0);
-    const u32 A = AesLds::ld(a0);
-    u32 n0 = xor3(xor3(A, rotr8(T.te0_b<2>(s1)), rotr16(T.te0_b<1>(s2))),
-                  rotr24(t30), k0);
-    u32 n1 = xor3(xor3(T.te0_b<3>(s1), rotr8(T.te0_b<2>(s2)), rotr16(t31)),
-                  rotr24(T.te0_b<0>(s0)), k1);
-    u32 n2 = xor3(xor3(T.te0_b<3>(s2), rotr8(t32), rotr16(T.te0_b<1>(s0))),
-                  rotr24(T.te0_b<0>(s1)), k2);
-    u32 n3 = xor3(xor3(t33, rotr8(T.te0_b<2>(s0)), rotr16(T.te0_b<1>(s1))),
-                  rotr24(T.te0_b<0>(s2)), k3);
-    // child b differs in bit 0 of byte (s0 >> 24): entry index ^ 1 is
-    // address ^ 256
-    const u32 m0 = xor3(n0, A, AesLds::ld(a0 ^ 256u));
-    // round 2
+    const u32 n0 = s0, n1 = s1, n2 = s2, n3 = s3, m0 = u0;
+    // every output word shares three of its four lookups, and word 0 its
+    // rotated half as well
     next_round_key();
-    const u32 c0 = xor3(rotr8(T.te0_b<2>(n1)), rotr16(T.te0_b<1>(n2)),
-                        rotr24(T.te0_b<0>(n3))) ^ k0;
-    const u32 c1 = xor3(T.te0_b<3>(n1), rotr8(T.te0_b<2>(n2)),
-                        rotr16(T.te0_b<1>(n3))) ^ k1;
-    const u32 c2 = xor3(T.te0_b<3>(n2), rotr8(T.te0_b<2>(n3)),
-                        rotr24(T.te0_b<0>(n1))) ^ k2;
-    const u32 c3 = xor3(T.te0_b<3>(n3), rotr16(T.te0_b<1>(n1)),
-                        rotr24(T.te0_b<0>(n2))) ^ k3;
-    s0 = T.te0_b<3>(n0) ^ c0;
-    u0 = T.te0_b<3>(m0) ^ c0;
-    s1 = rotr24(T.te0_b<0>(n0)) ^ c1;
-    u1 = rotr24(T.te0_b<0>(m0)) ^ c1;
-    s2 = rotr16(T.te0_b<1>(n0)) ^ c2;
-    u2 = rotr16(T.te0_b<1>(m0)) ^ c2;
-    s3 = rotr8(T.te0_b<2>(n0)) ^ c3;
-    u3 = rotr8(T.te0_b<2>(m0)) ^ c3;
+    const u32 e13 = T.te0_b<3>(n1), e12 = T.te0_b<2>(n1),
+              e11 = T.te2_b<1>(n1), e10 = T.te2_b<0>(n1);
+    const u32 e23 = T.te0_b<3>(n2), e22 = T.te0_b<2>(n2),
+              e21 = T.te2_b<1>(n2), e20 = T.te2_b<0>(n2);
+    const u32 e33 = T.te0_b<3>(n3), e32 = T.te0_b<2>(n3),
+              e31 = T.te2_b<1>(n3), e30 = T.te2_b<0>(n3);
+    const u32 r0 = rotr8(xor3(e12, e30, q0));
+    s0 = xor3(T.te0_b<3>(n0), e21, r0);
+    u0 = xor3(T.te0_b<3>(m0), e21, r0);
+    s1 = AesLds::mix(e13, e22, e31, T.te2_b<0>(n0), q1);
+    u1 = AesLds::mix(e13, e22, e31, T.te2_b<0>(m0), q1);
+    s2 = AesLds::mix(e23, e32, T.te2_b<1>(n0), e10, q2);
+    u2 = AesLds::mix(e23, e32, T.te2_b<1>(m0), e10, q2);
+    s3 = AesLds::mix(e33, T.te0_b<2>(n0), e11, e20, q3);
+    u3 = AesLds::mix(e33, T.te0_b<2>(m0), e11, e20, q3);
     r_begin = 3;
   }
 #endif
@@ -411,35 +476,35 @@ __device__ __forceinline__ void aes_cipher_pair(uint4 seed, const AesLds& T,
   for (int r = r_begin; r < 10; ++r) {
     next_round_key();
     // cipher round r for both children
-    u32 n0 = T.col(s0, s1, s2, s3, k0);
-    u32 m0 = T.col(u0, u1, u2, u3, k0);
-    u32 n1 = T.col(s1, s2, s3, s0, k1);
-    u32 m1 = T.col(u1, u2, u3, u0, k1);
-    u32 n2 = T.col(s2, s3, s0, s1, k2);
-    u32 m2 = T.col(u2, u3, u0, u1, k2);
-    u32 n3 = T.col(s3, s0, s1, s2, k3);
-    u32 m3 = T.col(u3, u0, u1, u2, k3);
+    u32 n0 = T.col(s0, s1, s2, s3, q0);
+    u32 m0 = T.col(u0, u1, u2, u3, q0);
+    u32 n1 = T.col(s1, s2, s3, s0, q1);
+    u32 m1 = T.col(u1, u2, u3, u0, q1);
+    u32 n2 = T.col(s2, s3, s0, s1, q2);
+    u32 m2 = T.col(u2, u3, u0, u1, q2);
+    u32 n3 = T.col(s3, s0, s1, s2, q3);
+    u32 m3 = T.col(u3, u0, u1, u2, q3);
     s0 = n0; s1 = n1; s2 = n2; s3 = n3;
     u0 = m0; u1 = m1; u2 = m2; u3 = m3;
   }
-  next_round_key();  // round 10
-  u32 o0 = T.last(s0, s1, s2, s3, k0);
-  u32 p0 = T.last(u0, u1, u2, u3, k0);
+  next_round_key();  // round 10; its output words come out as rol8(.)
+  u32 o0 = T.last(s0, s1, s2, s3, q0);
+  u32 p0 = T.last(u0, u1, u2, u3, q0);
   if constexpr (LOW) {
-    ra = make_uint4(__builtin_bswap32(o0), 0, 0, 0);
-    rb = make_uint4(__builtin_bswap32(p0), 0, 0, 0);
+    ra = make_uint4(bswap_rol8(o0), 0, 0, 0);
+    rb = make_uint4(bswap_rol8(p0), 0, 0, 0);
     return;
   }
-  u32 o1 = T.last(s1, s2, s3, s0, k1);
-  u32 p1 = T.last(u1, u2, u3, u0, k1);
-  u32 o2 = T.last(s2, s3, s0, s1, k2);
-  u32 p2 = T.last(u2, u3, u0, u1, k2);
-  u32 o3 = T.last(s3, s0, s1, s2, k3);
-  u32 p3 = T.last(u3, u0, u1, u2, k3);
-  ra = make_uint4(__builtin_bswap32(o0), __builtin_bswap32(o1),
-                  __builtin_bswap32(o2), __builtin_bswap32(o3));
-  rb = make_uint4(__builtin_bswap32(p0), __builtin_bswap32(p1),
-                  __builtin_bswap32(p2), __builtin_bswap32(p3));
+  u32 o1 = T.last(s1, s2, s3, s0, q1);
+  u32 p1 = T.last(u1, u2, u3, u0, q1);
+  u32 o2 = T.last(s2, s3, s0, s1, q2);
+  u32 p2 = T.last(u2, u3, u0, u1, q2);
+  u32 o3 = T.last(s3, s0, s1, s2, q3);
+  u32 p3 = T.last(u3, u0, u1, u2, q3);
+  ra = make_uint4(bswap_rol8(o0), bswap_rol8(o1), bswap_rol8(o2),
+                  bswap_rol8(o3));
+  rb = make_uint4(bswap_rol8(p0), bswap_rol8(p1), bswap_rol8(p2),
+                  bswap_rol8(p3));
 }
 
 // ---------------------------------------------------------------------------
