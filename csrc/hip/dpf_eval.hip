@@ -73,7 +73,7 @@ constexpr int MAX_LDS_LEVELS = 4;
 // Most (key, segment) units one AES workgroup walks (they share the table)
 constexpr int AES_MAX_UNITS = 4;
 // The same for rows wider than 16 words.  The K = 4 kernel lives in 128
-// VGPRs and uses all of them at 16 words, so it has no room for the 16*W
+// VGPRs and uses 124 of them at 16 words, so it has no room for the 16*W
 // accumulators of a wide row; at K <= 2 a workgroup is at most 8 waves and
 // a wave may take 256.
 constexpr int AES_MAX_UNITS_WIDE = 2;
@@ -385,6 +385,18 @@ __global__ __launch_bounds__(256 * K) void dpf_eval_kernel(
             acc_c[4 * q + 2] += v0 * r0q[q].z + v1 * r1q[q].z;
             acc_c[4 * q + 3] += v0 * r0q[q].w + v1 * r1q[q].w;
           }
+          // Left alone the compiler sinks these MACs below the pop-and-
+          // descend loop, so a block of row data (32 VGPRs) stays live
+          // through the pair expansions.  The batched AES cipher needs
+          // those registers for its lookups in flight (with them K = 4
+          // spills at every batch depth), so the sums are made to exist
+          // here.  The statement emits no instruction.
+          if constexpr (PRF == PRF_AES128 && AES_BATCH != 0) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+              asm volatile("" : "+v"(acc_c[4 * q]), "+v"(acc_c[4 * q + 1]),
+                                "+v"(acc_c[4 * q + 2]), "+v"(acc_c[4 * q + 3]));
+          }
         }
       } else {
         u32* orow = out + (u64)key_id * (u64)n +
@@ -469,7 +481,9 @@ int slog_for(int batch, int DS) {
 // measured at n = 2^20, batch 512 on MI355X (profiles/PROFILING.md) a
 // round of 1/2/3/4 units took 3.6/4.6/5.2/7.5 ms (2.9/3.7/4.5/6.4 ms since
 // the te0/te2 table rows: nearly the same ratios, so round_cost keeps the
-// first set and no choice changes).  Take the K with the
+// first set and no choice changes; 2.4/3.5/4.3/6.1 ms with the batched
+// cipher, which would move only 6913..7168 units from K = 3 to K = 4, for
+// 1.6% of that launch).  Take the K with the
 // cheapest rounds x cost, the smallest on ties: 2048 units -> K = 4 (2
 // rounds on 256 CUs); 1200 units -> K = 3; a single key's 256 segments ->
 // K = 1 (one unit on every CU).  GPUDPF_AES_UNITS=1..4 forces K, for A/B
