@@ -387,11 +387,11 @@ __global__ __launch_bounds__(256 * K) void dpf_eval_kernel(
           }
           // Left alone the compiler sinks these MACs below the pop-and-
           // descend loop, so a block of row data (32 VGPRs) stays live
-          // through the pair expansions.  The batched AES cipher needs
-          // those registers for its lookups in flight (with them K = 4
-          // spills at every batch depth), so the sums are made to exist
-          // here.  The statement emits no instruction.
-          if constexpr (PRF == PRF_AES128 && AES_BATCH != 0) {
+          // through the pair expansions.  The AES cipher needs those
+          // registers for its lookups in flight (with them K = 4 spills),
+          // so the sums are made to exist here.  The statement emits no
+          // instruction.
+          if constexpr (PRF == PRF_AES128) {
 #pragma unroll
             for (int q = 0; q < 4; ++q)
               asm volatile("" : "+v"(acc_c[4 * q]), "+v"(acc_c[4 * q + 1]),

@@ -347,29 +347,19 @@ struct AesLds {
                                             u32 te2d, u32 q) {
     return xor3(te0a, te2c, rotr8(xor3(te0b, te2d, q)));
   }
+  // One output word in two halves: *_issue starts its four reads, and the
+  // combine (mix, last, key of the Words) may come any time later.
+  struct Words { u32 a, b, c, d; };
   // One MixColumns output word: te0[a.b3] ^ te1[b.b2] ^ te2[c.b1] ^
   // te3[d.b0] ^ k, given q = rol8(k)
-  __device__ __forceinline__ u32 col(u32 a, u32 b, u32 c, u32 d, u32 q) const {
-    return mix(te0_b<3>(a), te0_b<2>(b), te2_b<1>(c), te2_b<0>(d), q);
-  }
-  // One last-round output word, rotated like its key word:
-  // rol8([S(a.b3) S(b.b2) S(c.b1) S(d.b0)] ^ k), given q = rol8(k)
-  __device__ __forceinline__ u32 last(u32 a, u32 b, u32 c, u32 d, u32 q) const {
-    return xor3(aes_sb_pair<0, 3>(te0_b<3>(a), te0_b<2>(b)),
-                aes_sb_pair<2, 1>(te0_b<1>(c), te0_b<0>(d)), q);
-  }
-
-  // The same three in two halves, for the batched cipher: *_issue forms the
-  // four addresses and starts the four reads of one output word, and the
-  // combine (mix(Words, q), last(Words, q), key(Words, q0)) may come any
-  // number of instructions later.
-  struct Words { u32 a, b, c, d; };
   __device__ __forceinline__ Words col_issue(u32 a, u32 b, u32 c, u32 d) const {
     return {te0_b<3>(a), te0_b<2>(b), te2_b<1>(c), te2_b<0>(d)};
   }
   static __device__ __forceinline__ u32 mix(const Words& l, u32 q) {
     return mix(l.a, l.b, l.c, l.d, q);
   }
+  // One last-round output word, rotated like its key word:
+  // rol8([S(a.b3) S(b.b2) S(c.b1) S(d.b0)] ^ k), given q = rol8(k)
   __device__ __forceinline__ Words last_issue(u32 a, u32 b, u32 c,
                                               u32 d) const {
     return {te0_b<3>(a), te0_b<2>(b), te0_b<1>(c), te0_b<0>(d)};
@@ -377,8 +367,8 @@ struct AesLds {
   static __device__ __forceinline__ u32 last(const Words& l, u32 q) {
     return xor3(aes_sb_pair<0, 3>(l.a, l.b), aes_sb_pair<2, 1>(l.c, l.d), q);
   }
-  // SubWord(RotWord(.)) of the key schedule, read from q3 = rol8(k3) as in
-  // next_round_key; key() is the new q0 before the round constant
+  // SubWord(RotWord(.)) of the key schedule reads q3 = rol8(k3) as it would
+  // read k3; key() is the new q0 before the round constant (in byte 0)
   __device__ __forceinline__ Words key_issue(u32 q3) const {
     return {te0_b<2>(q3), te0_b<1>(q3), te0_b<0>(q3), te0_b<3>(q3)};
   }
@@ -386,35 +376,6 @@ struct AesLds {
     return xor3(aes_sb_pair<3, 2>(l.a, l.b), aes_sb_pair<1, 0>(l.c, l.d), q0);
   }
 };
-
-// Batch depth of aes_cipher_pair: how many of the pair's T-table lookups are
-// issued before the first of them is combined.
-//   0       the compiler's order: it clusters two to six reads, waits for
-//           them and combines them (one s_waitcnt per 1.85 lookups).
-//   4..16   that many lookups in flight, rolling by output word: a word of
-//           one child is combined, then a word of the other issued.
-//   32      both children's rounds in flight; child a's round r is combined
-//           and its round r+1 issued while child b's round r is in flight,
-//           and the other way round.
-// It is a template argument of the cipher; every kernel takes the default,
-// AES_BATCH, because every instantiation has the registers for any depth
-// (docs/KERNEL_NOTES.md, "Static record of the batched cipher").  Measured
-// (profiles/PROFILING.md): at n = 2^20 every depth from 4 to 32 is within
-// 1.5% of the others, and 32 is the one that is also faster than depth 0
-// on a small table.  gfx950's s_waitcnt counts at most 15 LDS operations,
-// so with more in flight the first wait of a batch cannot name the read it
-// needs and drains down to 14 instead: more depth than 16 buys no more
-// reads in flight at a wait.
-// For A/B builds: -DGPUDPF_AES_BATCH=<depth> sets the default, and
-// -DGPUDPF_AES_NOBATCH is depth 0, with which every kernel is instruction
-// for instruction the one from before the batched cipher.
-#if defined(GPUDPF_AES_NOBATCH)
-constexpr int AES_BATCH = 0;
-#elif defined(GPUDPF_AES_BATCH)
-constexpr int AES_BATCH = GPUDPF_AES_BATCH;
-#else
-constexpr int AES_BATCH = 32;
-#endif
 
 // Stage the table at LDS byte 0 (all threads of the workgroup; the caller
 // synchronizes); nothing for the other PRFs.  `lds0` must be the start of
@@ -449,37 +410,25 @@ __device__ __forceinline__ AesLds aes_lds_init(
 // latency chain (PMC: SQ_WAIT_ANY was 31.5% of wave cycles with the
 // standalone schedule).  Also drops the rk[44] register array.
 //
-// DEPTH (AES_BATCH above) > 0 pins the order of lookups and combines with
-// __builtin_amdgcn_sched_barrier(0) between the phases; the s_waitcnt are
-// the compiler's own, counted because LDS reads return in order.  The
-// lookups, the algebra and the results are those of DEPTH = 0.
-template <bool LOW, int DEPTH = AES_BATCH>
+// __builtin_amdgcn_sched_barrier(0) pins the order of lookups and combines:
+// child a's round r is combined and its round r+1 issued (16 lookups) while
+// child b's round r is in flight, then the other way round.  The s_waitcnt
+// are the compiler's, counted because LDS reads return in order; one counts
+// at most 15 LDS operations on gfx950, so a round's first wait drains to 14
+// and issuing further ahead would leave no more in flight (KERNEL_NOTES.md).
+template <bool LOW>
 __device__ __forceinline__ void aes_cipher_pair(uint4 seed, const AesLds& T,
                                                 uint4& ra, uint4& rb) {
-  static_assert(DEPTH == 0 || DEPTH == 32 ||
-                    (DEPTH % 4 == 0 && DEPTH >= 4 && DEPTH <= 16),
-                "see AES_BATCH");
-  // The schedule runs on q = rol8(round key) throughout (header comment:
-  // Rotations).  Before round 1 the state is the key itself, so q0..q3 are
-  // also the state, read through the *_kb accessors.
+  // The key schedule runs on q = rol8(round key) (header: Rotations).  Before
+  // round 1 q0..q3 are also the state, read through the *_kb accessors.
   u32 q0 = bswap_rol8(seed.x), q1 = bswap_rol8(seed.y),
       q2 = bswap_rol8(seed.z), q3 = bswap_rol8(seed.w);
   u32 rcon = 0x02u;
-  // next round key (q0..q3 = rol8 of rk[4r-4..4r-1] become those of
-  // rk[4r..4r+3]): SubWord(RotWord(.)) reads q3 as it would read k3, and
-  // the round constant sits in byte 0
-  auto next_round_key = [&] {
-    q0 = xor3(aes_sb_pair<3, 2>(T.te0_b<2>(q3), T.te0_b<1>(q3)),
-              aes_sb_pair<1, 0>(T.te0_b<0>(q3), T.te0_b<3>(q3)), q0) ^ rcon;
-    rcon = (rcon << 1) ^ ((rcon & 0x80u) ? 0x11bu : 0u);
-    rcon &= 0xffu;
-    q1 ^= q0; q2 ^= q1; q3 ^= q2;
-  };
   // Round 1.  The two children's plaintexts (pos 0 / pos 1) differ in a
   // single byte, so their states agree except for byte 3 of word 0: the 16
   // lookups x<word><byte> below are both children's, and child b costs ONE
   // more (x03b).  Bytes 3 and 2 of a word are read from te0, bytes 1 and 0
-  // from te2, as AesLds::col does.
+  // from te2, as col_issue does.
   const u32 a0 = T.addr_kb<3>(q0);
   const u32 x03 = AesLds::ld(a0), x02 = T.te0_kb<2>(q0),
             x01 = T.te2_kb<1>(q0), x00 = T.te2_kb<0>(q0);
@@ -491,11 +440,10 @@ __device__ __forceinline__ void aes_cipher_pair(uint4 seed, const AesLds& T,
             x31 = T.te2_kb<1>(q3), x30 = T.te2_kb<0>(q3);
   // bit 0 of that byte flips: entry index ^ 1 is address ^ 256
   const u32 x03b = AesLds::ld(a0 ^ 256u);
-  if constexpr (DEPTH > 0) __builtin_amdgcn_sched_barrier(0);  // 17 in flight
+  __builtin_amdgcn_sched_barrier(0);  // 17 in flight
   // Round 1's key.  Word 3 of the state is the key word k3 (the position
   // byte only enters word 0), so x33..x30 also carry the sbox bytes of the
-  // round-1 key schedule (byte 2 of a te0 word, byte 0 of a te2 word): no
-  // separate sbox lookups, hence no next_round_key.
+  // round-1 key schedule (byte 2 of a te0 word, byte 0 of a te2 word).
   // rol8([S(b2) S(b1) S(b0) S(b3)]) = [S(b1) S(b0) S(b3) S(b2)] of k3
   q0 = xor3(aes_sb_pair<3, 2, 0, 0>(x31, x30), aes_sb_pair<1, 0>(x33, x32),
             q0) ^ 0x01u;
@@ -506,155 +454,78 @@ __device__ __forceinline__ void aes_cipher_pair(uint4 seed, const AesLds& T,
   u32 s3 = AesLds::mix(x33, x02, x11, x20, q3);
   // the un-rotated te0 term is the one that differs
   u32 u0 = xor3(s0, x03, x03b), u1 = s1, u2 = s2, u3 = s3;
-  if constexpr (DEPTH > 0) {
-    // Rounds 2..10, batched.  l[c][i] are the looked-up words of output
-    // word i of child c's round in flight, st[c] the state they were
-    // issued from, q the key of the round being combined.  `kw`, the four
-    // sbox lookups of the next key, is issued a round ahead of the combine
-    // that needs it, so it has always returned.
-    using Words = AesLds::Words;
-    u32 q[4] = {q0, q1, q2, q3};
-    Words kw = T.key_issue(q[3]);
-    auto key_step = [&](bool issue_next) {
-      q[0] = AesLds::key(kw, q[0]) ^ rcon;
-      rcon = (rcon << 1) ^ ((rcon & 0x80u) ? 0x11bu : 0u);
-      rcon &= 0xffu;
-      q[1] ^= q[0]; q[2] ^= q[1]; q[3] ^= q[2];
-      if (issue_next) kw = T.key_issue(q[3]);
-    };
-#ifndef GPUDPF_AES_NOSHARE
-    // Shared round 2 (below): the lookups of state words 1..3 are both
-    // children's, e<j> = bytes 3, 2 (te0) and 1, 0 (te2) of word j
-    const Words e1 = T.col_issue(s1, s1, s1, s1),
-                e2 = T.col_issue(s2, s2, s2, s2),
-                e3 = T.col_issue(s3, s3, s3, s3);
-#endif
-    // is output word i of round r needed at all
-    auto need = [](int i, int r) { return !(LOW && r == 10 && i > 0); };
-    // start the lookups of output word i of round r from the state x
-    auto issue = [&](const u32 (&x)[4], int i, int r) -> Words {
-#ifndef GPUDPF_AES_NOSHARE
-      if (r == 2) {  // only the byte of word 0 is the child's own
-        switch (i) {
-          case 0: return {T.te0_b<3>(x[0]), e1.b, e2.c, e3.d};
-          case 1: return {e1.a, e2.b, e3.c, T.te2_b<0>(x[0])};
-          case 2: return {e2.a, e3.b, T.te2_b<1>(x[0]), e1.d};
-          default: return {e3.a, T.te0_b<2>(x[0]), e1.c, e2.d};
-        }
+  // Rounds 2..10.  q is rol8 of the key of the round being combined; `kw`,
+  // the four sbox lookups of the next key, is issued a round ahead of the
+  // combine that needs it, so it has always returned.
+  using Words = AesLds::Words;
+  u32 q[4] = {q0, q1, q2, q3};
+  Words kw = T.key_issue(q[3]);
+  auto key_step = [&](bool issue_next) {
+    q[0] = AesLds::key(kw, q[0]) ^ rcon;
+    rcon = (rcon << 1) ^ ((rcon & 0x80u) ? 0x11bu : 0u);
+    rcon &= 0xffu;
+    q[1] ^= q[0]; q[2] ^= q[1]; q[3] ^= q[2];
+    if (issue_next) kw = T.key_issue(q[3]);
+  };
+  // Shared round 2: the states still agree in words 1..3 and each output
+  // word reads one byte of word 0, so 12 of the 16 lookups are both children's
+  // (~27 of ~320 per pair with round 1's): e<j> = te0, te0, te2, te2 of word j
+  const Words e1 = T.col_issue(s1, s1, s1, s1),
+              e2 = T.col_issue(s2, s2, s2, s2),
+              e3 = T.col_issue(s3, s3, s3, s3);
+  // is output word i of round r needed at all
+  auto need = [](int i, int r) { return !(LOW && r == 10 && i > 0); };
+  // start the lookups of output word i of round r from the state x
+  auto issue = [&](const u32 (&x)[4], int i, int r) -> Words {
+    if (r == 2) {  // only the byte of word 0 is the child's own
+      switch (i) {
+        case 0: return {T.te0_b<3>(x[0]), e1.b, e2.c, e3.d};
+        case 1: return {e1.a, e2.b, e3.c, T.te2_b<0>(x[0])};
+        case 2: return {e2.a, e3.b, T.te2_b<1>(x[0]), e1.d};
+        default: return {e3.a, T.te0_b<2>(x[0]), e1.c, e2.d};
       }
-#endif
-      const u32 a = x[i], b = x[(i + 1) & 3], c = x[(i + 2) & 3],
-                d = x[(i + 3) & 3];
-      return r == 10 ? T.last_issue(a, b, c, d) : T.col_issue(a, b, c, d);
-    };
-    // The lookups form a stream of jobs, one output word each: round 2
-    // child a words 0..3, child b words 0..3, round 3 child a ... round 10.
-    // A step combines G words issued WN words earlier, issues the next G
-    // and ends at a scheduling barrier.  Depth 32 steps by a child's whole
-    // round (a's round r-1 is combined and its round r issued while b's
-    // round r-1 is in flight, then the other way round); the smaller depths
-    // roll word by word.  A child's round is issued from its state after
-    // all four words of its last round, which are at least five jobs back:
-    // hence WN <= 4 when rolling by word.
-    constexpr int G = DEPTH == 32 ? 4 : 1;
-    constexpr int WN = DEPTH / 4;
-    constexpr int JOBS = 9 * 8;
-    Words l[2][4];
-    u32 st[2][4] = {{s0, s1, s2, s3}, {u0, u1, u2, u3}}, n[2][4];
-    u32 out[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
-#pragma unroll
-    for (int k = 0; k < JOBS + WN; k += G) {
-#pragma unroll
-      for (int j = k - WN; j < k - WN + G; ++j) {
-        if (j < 0) continue;
-        const int c = (j >> 2) & 1, i = j & 3, r = 2 + (j >> 3);
-        if ((j & 7) == 0) key_step(r < 10);  // round r's key
-        if (!need(i, r)) continue;
-        if (r == 10) {  // comes out as rol8(.)
-          out[c][i] = bswap_rol8(AesLds::last(l[c][i], q[i]));
-        } else {
-          n[c][i] = AesLds::mix(l[c][i], q[i]);
-          if (i == 3) {
-#pragma unroll
-            for (int w = 0; w < 4; ++w) st[c][w] = n[c][w];
-          }
-        }
-      }
-#pragma unroll
-      for (int j = k; j < k + G && j < JOBS; ++j) {
-        const int c = (j >> 2) & 1, i = j & 3, r = 2 + (j >> 3);
-        if (need(i, r)) l[c][i] = issue(st[c], i, r);
-      }
-      __builtin_amdgcn_sched_barrier(0);
     }
-    ra = make_uint4(out[0][0], out[0][1], out[0][2], out[0][3]);
-    rb = make_uint4(out[1][0], out[1][1], out[1][2], out[1][3]);
-    return;
-  }
-  int r_begin = 2;
-#ifndef GPUDPF_AES_NOSHARE
-  // Shared round 2: the states still agree in words 1..3, and each output
-  // word reads exactly one byte of the diverged word 0, so round 2 shares
-  // 12 of its 16 lookups.  With round 1 that saves ~27 of ~320 lookups per
-  // pair; rounds 3+ are fully diverged and run the common loop below.
-  // A/B toggle: compile with -DGPUDPF_AES_NOSHARE to run round 2 in the
-  // common loop as well (measured comparison in profiles/PROFILING.md).
-  {
-    const u32 n0 = s0, n1 = s1, n2 = s2, n3 = s3, m0 = u0;
-    // every output word shares three of its four lookups, and word 0 its
-    // rotated half as well
-    next_round_key();
-    const u32 e13 = T.te0_b<3>(n1), e12 = T.te0_b<2>(n1),
-              e11 = T.te2_b<1>(n1), e10 = T.te2_b<0>(n1);
-    const u32 e23 = T.te0_b<3>(n2), e22 = T.te0_b<2>(n2),
-              e21 = T.te2_b<1>(n2), e20 = T.te2_b<0>(n2);
-    const u32 e33 = T.te0_b<3>(n3), e32 = T.te0_b<2>(n3),
-              e31 = T.te2_b<1>(n3), e30 = T.te2_b<0>(n3);
-    const u32 r0 = rotr8(xor3(e12, e30, q0));
-    s0 = xor3(T.te0_b<3>(n0), e21, r0);
-    u0 = xor3(T.te0_b<3>(m0), e21, r0);
-    s1 = AesLds::mix(e13, e22, e31, T.te2_b<0>(n0), q1);
-    u1 = AesLds::mix(e13, e22, e31, T.te2_b<0>(m0), q1);
-    s2 = AesLds::mix(e23, e32, T.te2_b<1>(n0), e10, q2);
-    u2 = AesLds::mix(e23, e32, T.te2_b<1>(m0), e10, q2);
-    s3 = AesLds::mix(e33, T.te0_b<2>(n0), e11, e20, q3);
-    u3 = AesLds::mix(e33, T.te0_b<2>(m0), e11, e20, q3);
-    r_begin = 3;
-  }
-#endif
+    const u32 a = x[i], b = x[(i + 1) & 3], c = x[(i + 2) & 3],
+              d = x[(i + 3) & 3];
+    return r == 10 ? T.last_issue(a, b, c, d) : T.col_issue(a, b, c, d);
+  };
+  // The lookups form a stream of 72 jobs, one output word each: round 2
+  // child a words 0..3, child b words 0..3, round 3 child a ... round 10.
+  // A step combines one child's round of four words, issued eight jobs
+  // earlier, from l[c] into the state st[c], issues its next round and ends
+  // at a scheduling barrier.  The barriers pin the phases, not the order
+  // inside one: writing st[c][i] without n[], or looping over (round, child)
+  // and i, is the same algebra but reorders a word's ds_read_b32 (tried).
+  Words l[2][4];
+  u32 st[2][4] = {{s0, s1, s2, s3}, {u0, u1, u2, u3}}, n[2][4];
+  u32 out[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
 #pragma unroll
-  for (int r = r_begin; r < 10; ++r) {
-    next_round_key();
-    // cipher round r for both children
-    u32 n0 = T.col(s0, s1, s2, s3, q0);
-    u32 m0 = T.col(u0, u1, u2, u3, q0);
-    u32 n1 = T.col(s1, s2, s3, s0, q1);
-    u32 m1 = T.col(u1, u2, u3, u0, q1);
-    u32 n2 = T.col(s2, s3, s0, s1, q2);
-    u32 m2 = T.col(u2, u3, u0, u1, q2);
-    u32 n3 = T.col(s3, s0, s1, s2, q3);
-    u32 m3 = T.col(u3, u0, u1, u2, q3);
-    s0 = n0; s1 = n1; s2 = n2; s3 = n3;
-    u0 = m0; u1 = m1; u2 = m2; u3 = m3;
+  for (int k = 0; k < 72 + 8; k += 4) {
+#pragma unroll
+    for (int j = k - 8; j < k - 4; ++j) {
+      if (j < 0) continue;
+      const int c = (j >> 2) & 1, i = j & 3, r = 2 + (j >> 3);
+      if ((j & 7) == 0) key_step(r < 10);  // round r's key
+      if (!need(i, r)) continue;
+      if (r == 10) {  // comes out as rol8(.)
+        out[c][i] = bswap_rol8(AesLds::last(l[c][i], q[i]));
+      } else {
+        n[c][i] = AesLds::mix(l[c][i], q[i]);
+        if (i == 3) {
+#pragma unroll
+          for (int w = 0; w < 4; ++w) st[c][w] = n[c][w];
+        }
+      }
+    }
+#pragma unroll
+    for (int j = k; j < k + 4 && j < 72; ++j) {
+      const int c = (j >> 2) & 1, i = j & 3, r = 2 + (j >> 3);
+      if (need(i, r)) l[c][i] = issue(st[c], i, r);
+    }
+    __builtin_amdgcn_sched_barrier(0);
   }
-  next_round_key();  // round 10; its output words come out as rol8(.)
-  u32 o0 = T.last(s0, s1, s2, s3, q0);
-  u32 p0 = T.last(u0, u1, u2, u3, q0);
-  if constexpr (LOW) {
-    ra = make_uint4(bswap_rol8(o0), 0, 0, 0);
-    rb = make_uint4(bswap_rol8(p0), 0, 0, 0);
-    return;
-  }
-  u32 o1 = T.last(s1, s2, s3, s0, q1);
-  u32 p1 = T.last(u1, u2, u3, u0, q1);
-  u32 o2 = T.last(s2, s3, s0, s1, q2);
-  u32 p2 = T.last(u2, u3, u0, u1, q2);
-  u32 o3 = T.last(s3, s0, s1, s2, q3);
-  u32 p3 = T.last(u3, u0, u1, u2, q3);
-  ra = make_uint4(bswap_rol8(o0), bswap_rol8(o1), bswap_rol8(o2),
-                  bswap_rol8(o3));
-  rb = make_uint4(bswap_rol8(p0), bswap_rol8(p1), bswap_rol8(p2),
-                  bswap_rol8(p3));
+  ra = make_uint4(out[0][0], out[0][1], out[0][2], out[0][3]);
+  rb = make_uint4(out[1][0], out[1][1], out[1][2], out[1][3]);
 }
 
 // ---------------------------------------------------------------------------
