@@ -3,7 +3,8 @@
 
 The table is built directly in HBM (eval_init_empty + chunked on-GPU
 fill with a seeded generator) and NEVER exists on the host; DPF
-reconstruction is verified against table_read before timing.
+reconstruction is verified against table_read before timing.  (The exact
+single-server check at large offsets is tests/test_gpu_large_offsets.py.)
 
 Shapes:
   wide      n=2^28, e=224 u32  -> 240.5 GB table, two-stage streaming-GEMM

@@ -305,6 +305,9 @@ void launch_coop(std::uintptr_t keys, std::uintptr_t table, std::uintptr_t out,
                  std::uintptr_t aes_tabs, long long n, int depth, int zlog,
                  int prf, bool fused, std::uintptr_t stream) {
   check_domain(depth, n);
+  // the in-kernel leaf_perm shifts by 32 - zlog and 33 - (depth - zlog)
+  if (zlog < 6 || zlog >= depth)
+    throw std::invalid_argument("zlog must be in [6, depth)");
   const size_t half = (size_t)(n / 2) * sizeof(uint4);
   uint4* ping =
       static_cast<uint4*>(g_eval_scratch.get(2 * half > 0 ? 2 * half : 32));

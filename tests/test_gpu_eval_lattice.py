@@ -125,6 +125,21 @@ def test_naive_rejects_mismatched_domain(prf, depth, n):
                         prf=prf, stream=0)
 
 
+@pytest.mark.parametrize("depth,zlog", [(7, 5), (7, 7), (20, 20), (20, 0),
+                                        (20, -1), (32, 33)])
+@pytest.mark.parametrize("fused", [True, False])
+def test_coop_rejects_zlog_out_of_range(fused, depth, zlog):
+    """No GPU needed: the cooperative launcher checks zlog like the eval
+    launchers, before any HIP call (its in-kernel row permutation shifts by
+    32 - zlog and 33 - (depth - zlog))."""
+    if _hip is None:
+        pytest.skip("gpudpf._hip cannot be imported")
+    with pytest.raises(ValueError, match="zlog must be in"):
+        _hip.eval_coop(keys=0, table=0, out=0, aes_tabs=0, n=1 << depth,
+                       depth=depth, zlog=zlog, prf=DPF.PRF_DUMMY, fused=fused,
+                       stream=0)
+
+
 @functools.lru_cache(maxsize=None)
 def _table(depth):
     n = 1 << depth
