@@ -33,18 +33,21 @@ DpfKey key_from_array(const KeyArr& arr) {
   return k;
 }
 
-py::tuple gen(u64 alpha, u64 n, py::bytes seed, int prf_method) {
+// packed: four u32 leaves per seed (DpfKey in dpf_core.h); the default gives
+// the plain keys, byte for byte what this function gave before it existed.
+py::tuple gen(u64 alpha, u64 n, py::bytes seed, int prf_method, bool packed) {
   std::string s = seed;
   KeyRng rng(reinterpret_cast<const unsigned char*>(s.data()), s.size());
   DpfKey k0, k1;
-  dpf_gen(alpha, /*beta=*/1, n, prf_method, rng, k0, k1);
+  dpf_gen(alpha, /*beta=*/1, n, prf_method, rng, k0, k1,
+          packed ? kPackedLaneLog : 0);
   return py::make_tuple(key_to_array(k0), key_to_array(k1));
 }
 
 // Batched key generation: alphas int64[B] -> (k0s, k1s) int32[B,524].
 // One seeded RNG stream covers the whole batch (deterministic).
 py::tuple gen_batch(py::array_t<std::int64_t, py::array::c_style | py::array::forcecast> alphas,
-                    u64 n, py::bytes seed, int prf_method) {
+                    u64 n, py::bytes seed, int prf_method, bool packed) {
   std::string sd = seed;
   KeyRng rng(reinterpret_cast<const unsigned char*>(sd.data()), sd.size());
   const py::ssize_t b = alphas.size();
@@ -57,7 +60,8 @@ py::tuple gen_batch(py::array_t<std::int64_t, py::array::c_style | py::array::fo
     py::gil_scoped_release nogil;
     DpfKey k0, k1;
     for (py::ssize_t i = 0; i < b; ++i) {
-      dpf_gen((u64)ap[i], 1, n, prf_method, rng, k0, k1);
+      dpf_gen((u64)ap[i], 1, n, prf_method, rng, k0, k1,
+              packed ? kPackedLaneLog : 0);
       key_serialize(k0, p0 + i * kKeyInts);
       key_serialize(k1, p1 + i * kKeyInts);
     }
@@ -87,7 +91,8 @@ py::array_t<std::int32_t> expand_batch(const std::vector<KeyArr>& keys,
   for (size_t i = 0; i < b; ++i) ks[i] = key_from_array(keys[i]);
   const u64 n = ks[0].n;
   for (auto& k : ks)
-    if (k.n != n) throw std::invalid_argument("keys must share a domain size");
+    if (k.n != n || k.lane_log != ks[0].lane_log)
+      throw std::invalid_argument("keys must share a domain size and mode");
   py::array_t<std::int32_t> out({(py::ssize_t)b, (py::ssize_t)n});
   u32* optr = reinterpret_cast<u32*>(out.mutable_data());
   {
@@ -99,8 +104,9 @@ py::array_t<std::int32_t> expand_batch(const std::vector<KeyArr>& keys,
       // When keys are scarcer than threads, split each key's expansion
       // into W subtree shards (the residue-class restriction is itself a
       // DPF key; shard r's leaves are the strided slice out[r::W]).
+      // Packed keys have no subkeys: one task per key.
       u64 shards = 1;
-      while (b * shards < (size_t)num_threads &&
+      while (ks[0].lane_log == 0 && b * shards < (size_t)num_threads &&
              shards * 2 <= (ks[0].n >> 1) && shards < 64)
         shards <<= 1;
       std::vector<std::thread> pool;
@@ -137,6 +143,8 @@ u64 eval_point_low(const KeyArr& key, u64 idx, int prf_method) {
 
 py::tuple eval_point128(const KeyArr& key, u64 idx, int prf_method) {
   DpfKey k = key_from_array(key);
+  if (k.lane_log != 0)
+    throw std::invalid_argument("packed keys have u32 shares only");
   u128 v = dpf_eval_point(k, idx, prf_method);
   return py::make_tuple((u64)v, (u64)(v >> 64));
 }
@@ -191,6 +199,36 @@ py::array_t<std::int64_t> leaf_perm_rows(
   return out;
 }
 
+// The packed layout's maps (packed_perm in dpf_core.h); n is the table's row
+// count, 4 * 2^D.
+py::array_t<std::int64_t> packed_perm_table(u64 n, int zlog) {
+  py::array_t<std::int64_t> out((py::ssize_t)n);
+  auto* p = out.mutable_data();
+  {
+    py::gil_scoped_release nogil;
+    for (u64 i = 0; i < n; ++i) p[i] = (std::int64_t)packed_perm(n, zlog, i);
+  }
+  return out;
+}
+
+py::array_t<std::int64_t> packed_perm_rows(
+    py::array_t<std::int64_t, py::array::c_style | py::array::forcecast> idx,
+    u64 n, int zlog) {
+  const auto m = idx.size();
+  py::array_t<std::int64_t> out(m);
+  auto* p = out.mutable_data();
+  const auto* q = idx.data();
+  {
+    py::gil_scoped_release nogil;
+    for (py::ssize_t i = 0; i < m; ++i) {
+      const u64 v = (u64)q[i];
+      if (v >= n) throw std::out_of_range("index out of range");
+      p[i] = (std::int64_t)packed_perm(n, zlog, v);
+    }
+  }
+  return out;
+}
+
 // Compact wire format: the 524-int format always carries 64 cw slots; a
 // depth-d key only uses 2d of them, so shallow-tree keys ship dead
 // bytes (the reference's SizeOf, dpf_base/dpf.h:474, counts the same
@@ -203,7 +241,7 @@ py::array_t<std::int32_t> key_compact(const KeyArr& key) {
   py::array_t<std::int32_t> out((py::ssize_t)((3 + 4 * d) * 4));
   std::int32_t* op = out.mutable_data();
   u128* slots = reinterpret_cast<u128*>(op);
-  slots[0] = (u128)(unsigned)d;
+  slots[0] = (u128)(unsigned)d | ((u128)(unsigned)k.lane_log << 32);
   for (int i = 0; i < 2 * d; ++i) {
     slots[1 + i] = k.cw[0][i];
     slots[1 + 2 * d + i] = k.cw[1][i];
@@ -218,21 +256,25 @@ KeyArr key_expand_compact(
   if (c.size() < 8 || c.size() % 4 != 0)
     throw std::invalid_argument("corrupt compact key: bad length");
   const u128* slots = reinterpret_cast<const u128*>(c.data());
-  const int d = (int)(u64)slots[0];
+  const int d = (int)c.data()[0], lane_log = (int)c.data()[1];
   if (d < 1 || d > kMaxDepth)
     throw std::invalid_argument("corrupt compact key: bad depth");
+  if (lane_log != 0 && lane_log != kPackedLaneLog)
+    throw std::invalid_argument("corrupt compact key: lane log not 0 or 2");
   if (c.size() != (py::ssize_t)((3 + 4 * d) * 4))
     throw std::invalid_argument("corrupt compact key: length != 16*(3+4d)");
   DpfKey k;
   k.depth = d;
+  k.lane_log = lane_log;
   for (int i = 0; i < 2 * d; ++i) {
     k.cw[0][i] = slots[1 + i];
     k.cw[1][i] = slots[1 + 2 * d + i];
   }
   k.root = slots[1 + 4 * d];
   k.n = (u64)slots[2 + 4 * d];
-  if (k.n != ((u64)1 << d))
-    throw std::invalid_argument("corrupt compact key: n != 2^depth");
+  if (k.n != ((u64)1 << (d + lane_log)))
+    throw std::invalid_argument(
+        "corrupt compact key: n != 2^(depth + lane log)");
   return key_to_array(k);
 }
 
@@ -370,9 +412,9 @@ py::array_t<std::int32_t> aes_gpu_tables() {
 PYBIND11_MODULE(_core, m) {
   m.doc() = "gpudpf CPU core (keygen, reference eval, layout)";
   m.def("gen", &gen, py::arg("alpha"), py::arg("n"), py::arg("seed"),
-        py::arg("prf_method"));
+        py::arg("prf_method"), py::arg("packed") = false);
   m.def("gen_batch", &gen_batch, py::arg("alphas"), py::arg("n"),
-        py::arg("seed"), py::arg("prf_method"));
+        py::arg("seed"), py::arg("prf_method"), py::arg("packed") = false);
   m.def("expand", &expand, py::arg("key"), py::arg("prf_method"));
   m.def("expand_batch", &expand_batch, py::arg("keys"), py::arg("prf_method"),
         py::arg("num_threads") = 1);
@@ -381,6 +423,8 @@ PYBIND11_MODULE(_core, m) {
   m.def("eval_fused_cpu", &eval_fused_cpu);
   m.def("leaf_perm_table", &leaf_perm_table);
   m.def("leaf_perm_rows", &leaf_perm_rows);
+  m.def("packed_perm_table", &packed_perm_table);
+  m.def("packed_perm_rows", &packed_perm_rows);
   m.def("zlog_for_depth", &zlog_for_depth);
   m.def("prf", &prf);
   m.def("aes_block", &aes_block);
@@ -396,6 +440,8 @@ PYBIND11_MODULE(_core, m) {
   m.attr("KEY_INTS") = py::int_(kKeyInts);
   m.attr("ENTRY_WORDS") = py::int_(kEntryWords);
   m.attr("MAX_FUSED_WORDS") = py::int_(kMaxFusedWords);
+  m.attr("PACKED_LANE_LOG") = py::int_(kPackedLaneLog);
+  m.attr("PACKED_MIN_DOMAIN") = py::int_((long long)kPackedMinDomain);
   m.attr("PRF_DUMMY") = py::int_((int)PRF_DUMMY);
   m.attr("PRF_SALSA20") = py::int_((int)PRF_SALSA20);
   m.attr("PRF_CHACHA20") = py::int_((int)PRF_CHACHA20);

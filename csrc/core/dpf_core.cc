@@ -58,17 +58,54 @@ u128 KeyRng::next_odd_u128() { return next_u128() | 1; }
 // using payload beta_i we have s0 - s1 == beta_i (odd => parities differ,
 // so the two servers always select opposite correction words on the path;
 // off the path the seeds coincide and all contributions cancel).
+namespace {
+
+// Four independent u32 additions / subtractions (no carries between words):
+// the arithmetic of a packed key's last level.
+inline u128 add32x4(u128 a, u128 b) {
+  u128 r = 0;
+  for (int w = 0; w < 4; ++w)
+    r |= (u128)(u32)((u32)(a >> (32 * w)) + (u32)(b >> (32 * w))) << (32 * w);
+  return r;
+}
+inline u128 sub32x4(u128 a, u128 b) {
+  u128 r = 0;
+  for (int w = 0; w < 4; ++w)
+    r |= (u128)(u32)((u32)(a >> (32 * w)) - (u32)(b >> (32 * w))) << (32 * w);
+  return r;
+}
+// PRF output + correction word at eval level i of key k
+inline u128 add_cw(const DpfKey& k, int i, u128 p, u128 cw) {
+  return (k.lane_log != 0 && i == 0) ? add32x4(p, cw) : p + cw;
+}
+
+}  // namespace
+
+// Packed mode (lane_log = 2): the tree is walked on node = alpha & (2^D - 1)
+// with D = log2(n) - 2, and only level i = 0 changes: `other` and the
+// invariant are lane-wise, and the payload sits in word alpha >> D.  The
+// argument for that level is the one every level relies on: of each
+// correction-word pair one is fresh randomness and the other is masked by a
+// PRF output the other server cannot compute.
 void dpf_gen(u64 alpha, u128 beta, u64 n, int prf_method, KeyRng& rng,
-             DpfKey& k0, DpfKey& k1) {
+             DpfKey& k0, DpfKey& k1, int lane_log) {
+  if (lane_log != 0 && lane_log != kPackedLaneLog)
+    throw std::invalid_argument("lane_log must be 0 or 2");
   if (n < 2 || (n & (n - 1)) != 0)
     throw std::invalid_argument("n must be a power of two >= 2");
+  if (lane_log != 0 && n < kPackedMinDomain)
+    throw std::invalid_argument("packed keys need n >= 512");
   if (alpha >= n) throw std::invalid_argument("alpha must be < n");
-  const int depth = ilog2_u64(n);
+  const int depth = ilog2_u64(n) - lane_log;
   if (depth > kMaxDepth) throw std::invalid_argument("n too large");
+  const int lane = (int)(alpha >> depth);  // 0 for plain keys
+  alpha &= ((u64)1 << depth) - 1;
+  if (lane_log != 0) beta = (u128)(u32)beta << (32 * lane);
 
   k0 = DpfKey{};
   k1 = DpfKey{};
   k0.depth = k1.depth = depth;
+  k0.lane_log = k1.lane_log = lane_log;
   k0.n = k1.n = n;
 
   // Per-level payloads: the innermost level (i = depth-1, consumed first)
@@ -102,7 +139,9 @@ void dpf_gen(u64 alpha, u128 beta, u64 n, int prf_method, KeyRng& rng,
       // Let cw[sel(s0)] = rnd; solve cw[sel(s1)] so that
       //   (p0 + cw[sel0]) - (p1 + cw[sel1]) == (b == level_bit) ? beta_i : 0
       u128 target = (b == level_bit) ? beta_i : (u128)0;
-      u128 other = p0 + rnd - p1 - target;  // cw[sel1]
+      const bool lanes = lane_log != 0 && i == 0;  // lane-wise level
+      u128 other = lanes ? sub32x4(sub32x4(add32x4(p0, rnd), p1), target)
+                         : p0 + rnd - p1 - target;  // cw[sel1]
       int sel0 = (int)(s0 & 1);
       u128 cw_pair[2];
       cw_pair[sel0] = rnd;
@@ -116,13 +155,14 @@ void dpf_gen(u64 alpha, u128 beta, u64 n, int prf_method, KeyRng& rng,
     }
 
     // Advance the on-path seeds through this level.
-    u128 n0 = prf_eval(prf_method, s0, (u128)level_bit) +
-              cw_path[(size_t)(s0 & 1)];
-    u128 n1 = prf_eval(prf_method, s1, (u128)level_bit) +
-              cw_path[(size_t)(s1 & 1)];
+    u128 n0 = add_cw(k0, i, prf_eval(prf_method, s0, (u128)level_bit),
+                     cw_path[(size_t)(s0 & 1)]);
+    u128 n1 = add_cw(k0, i, prf_eval(prf_method, s1, (u128)level_bit),
+                     cw_path[(size_t)(s1 & 1)]);
     s0 = n0;
     s1 = n1;
-    if ((u128)(s0 - s1) != beta_i)
+    // (lane-wise at a packed key's last level: s0 - s1 == e_lane)
+    if ((lane_log != 0 && i == 0 ? sub32x4(s0, s1) : (u128)(s0 - s1)) != beta_i)
       throw std::logic_error("dpf_gen: level invariant violated");
     if (i > 0 && ((s0 ^ s1) & 1) == 0)
       throw std::logic_error("dpf_gen: parity invariant violated");
@@ -134,13 +174,14 @@ void dpf_gen(u64 alpha, u128 beta, u64 n, int prf_method, KeyRng& rng,
 // ---------------------------------------------------------------------------
 u128 dpf_eval_point(const DpfKey& k, u64 idx, int prf_method) {
   u128 key = k.root;
-  u64 rem = idx;
+  u64 rem = idx & (((u64)1 << k.depth) - 1);  // the node, for a packed key
   for (int i = k.depth - 1; i >= 0; --i) {
     int b = (int)(rem & 1);
     u128 v = prf_eval(prf_method, key, (u128)b);
-    key = v + k.cw[(size_t)(key & 1)][i * 2 + b];
+    key = add_cw(k, i, v, k.cw[(size_t)(key & 1)][i * 2 + b]);
     rem >>= 1;
   }
+  if (k.lane_log != 0) return (u128)(u32)(key >> (32 * (idx >> k.depth)));
   return key;
 }
 
@@ -175,8 +216,8 @@ inline void expand_children(const DpfKey& k, int prf_method, u128 seed, int i,
     p1 = prf_eval(prf_method, seed, 1);
   }
   int sel = (int)(seed & 1);
-  c0 = p0 + k.cw[sel][i * 2 + 0];
-  c1 = p1 + k.cw[sel][i * 2 + 1];
+  c0 = add_cw(k, i, p0, k.cw[sel][i * 2 + 0]);
+  c1 = add_cw(k, i, p1, k.cw[sel][i * 2 + 1]);
 }
 
 }  // namespace
@@ -185,8 +226,17 @@ inline void expand_children(const DpfKey& k, int prf_method, u128 seed, int i,
 // expansion is O(n log n) single calls: dpf_wrapper.cu:70-84).  Node arrays
 // are indexed by the partial natural index (consumed bit ell at weight
 // 2^ell), so leaves land in natural order directly.
+//
+// Packed keys: the tree has k.depth levels over the nodes, and a node's four
+// shares (the words of its leaf) go to node + lane * 2^depth.
 void dpf_expand_full(const DpfKey& k, int prf_method, u32* out) {
   const int depth = k.depth;
+  const int lanes = 1 << k.lane_log;
+  // leaf value c of node `node` -> its `lanes` natural positions
+  auto put = [&](u64 node, u128 c) {
+    for (int w = 0; w < lanes; ++w)
+      out[node + ((u64)w << depth)] = (u32)(c >> (32 * w));
+  };
   const bool vec8 = avx2_available() &&
                     (prf_method == PRF_SALSA20 || prf_method == PRF_CHACHA20);
   auto x8 = (prf_method == PRF_SALSA20) ? salsa12_x8 : chacha12_x8;
@@ -203,11 +253,11 @@ void dpf_expand_full(const DpfKey& k, int prf_method, u32* out) {
       x8(&cur[v], 1, p1v);
       for (int j = 0; j < 8; ++j) {
         const int sel = (int)(cur[v + j] & 1);
-        u128 c0 = p0v[j] + k.cw[sel][i * 2 + 0];
-        u128 c1 = p1v[j] + k.cw[sel][i * 2 + 1];
+        u128 c0 = add_cw(k, i, p0v[j], k.cw[sel][i * 2 + 0]);
+        u128 c1 = add_cw(k, i, p1v[j], k.cw[sel][i * 2 + 1]);
         if (i == 0) {
-          out[v + j] = (u32)c0;
-          out[(v + j) | ((u64)1 << l)] = (u32)c1;
+          put(v + j, c0);
+          put((v + j) | ((u64)1 << l), c1);
         } else {
           next[v + j] = c0;
           next[(v + j) | ((u64)1 << l)] = c1;
@@ -218,8 +268,8 @@ void dpf_expand_full(const DpfKey& k, int prf_method, u32* out) {
       u128 c0, c1;
       expand_children(k, prf_method, cur[v], i, c0, c1);
       if (i == 0) {
-        out[v] = (u32)c0;
-        out[v | ((u64)1 << l)] = (u32)c1;
+        put(v, c0);
+        put(v | ((u64)1 << l), c1);
       } else {
         next[v] = c0;
         next[v | ((u64)1 << l)] = c1;
@@ -248,7 +298,8 @@ void dpf_eval_fused_cpu(const DpfKey& k, int prf_method, const u32* table,
 void key_serialize(const DpfKey& k, std::int32_t out[kKeyInts]) {
   std::memset(out, 0, sizeof(std::int32_t) * kKeyInts);
   u128* slots = reinterpret_cast<u128*>(out);
-  slots[0] = (u128)(unsigned)k.depth;
+  // int 0 = depth, int 1 = lane log
+  slots[0] = (u128)(unsigned)k.depth | ((u128)(unsigned)k.lane_log << 32);
   for (int i = 0; i < 64; ++i) {
     slots[1 + i] = k.cw[0][i];
     slots[65 + i] = k.cw[1][i];
@@ -259,17 +310,20 @@ void key_serialize(const DpfKey& k, std::int32_t out[kKeyInts]) {
 
 void key_deserialize(const std::int32_t in[kKeyInts], DpfKey& k) {
   const u128* slots = reinterpret_cast<const u128*>(in);
-  k.depth = (int)(u64)slots[0];
+  k.depth = (int)in[0];
+  k.lane_log = (int)in[1];
   if (k.depth < 1 || k.depth > kMaxDepth)
     throw std::invalid_argument("corrupt key: bad depth");
+  if (k.lane_log != 0 && k.lane_log != kPackedLaneLog)
+    throw std::invalid_argument("corrupt key: lane log must be 0 or 2");
   for (int i = 0; i < 64; ++i) {
     k.cw[0][i] = slots[1 + i];
     k.cw[1][i] = slots[65 + i];
   }
   k.root = slots[129];
   k.n = (u64)slots[130];
-  if (k.n != ((u64)1 << k.depth))
-    throw std::invalid_argument("corrupt key: n != 2^depth");
+  if (k.n != ((u64)1 << (k.depth + k.lane_log)))
+    throw std::invalid_argument("corrupt key: n != 2^(depth + lane log)");
 }
 
 // ---------------------------------------------------------------------------
@@ -356,11 +410,25 @@ u64 leaf_perm_inv(u64 n, int zlog, u64 row) {
   return idx;
 }
 
+u64 packed_perm(u64 n, int zlog, u64 idx) {
+  const u64 nodes = n >> kPackedLaneLog;
+  return (leaf_perm(nodes, zlog, idx & (nodes - 1)) << kPackedLaneLog) |
+         (idx / nodes);
+}
+
+u64 packed_perm_inv(u64 n, int zlog, u64 row) {
+  const u64 nodes = n >> kPackedLaneLog;
+  const u64 lane = row & (((u64)1 << kPackedLaneLog) - 1);
+  return leaf_perm_inv(nodes, zlog, row >> kPackedLaneLog) + lane * nodes;
+}
+
 // ---------------------------------------------------------------------------
 // Sharding
 // ---------------------------------------------------------------------------
 void dpf_shard_subkey(const DpfKey& k, int prf_method, u64 rank, u64 world,
                       DpfKey& out) {
+  if (k.lane_log != 0)
+    throw std::invalid_argument("packed keys are not sharded");
   if (world < 1 || (world & (world - 1)) != 0)
     throw std::invalid_argument("world size must be a power of two");
   if (rank >= world) throw std::invalid_argument("rank must be < world");

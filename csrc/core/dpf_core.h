@@ -7,6 +7,8 @@
 //     (reference: dpf_base/dpf.h:403-464, DPF.md:45-91)
 //   - wire format: 524 x int32 = 131 u128 slots
 //     [depth][cw_1[64]][cw_2[64]][root][n]  (reference: dpf_wrapper.cu:26-46)
+//     Int 1 (inside the depth slot, zero in the reference's keys) is the
+//     lane log: 0 for plain keys, 2 for packed ones (DpfKey below).
 //   - PRFs: DUMMY / SALSA20(12) / CHACHA20(12) / AES128, bit-exact with the
 //     reference semantics (reference: dpf_base/dpf.h:65-235); verified by
 //     golden vectors in tests/test_prf_vectors.py.
@@ -95,9 +97,20 @@ constexpr int kKeyCwInt = 4;              // first correction-word int
 constexpr int kKeyRootInt = kKeyCwInt + 2 * kCwPerSel * 4;  // root seed (516)
 static_assert(kKeyRootInt + 2 * 4 == kKeyInts, "key = depth|cw|root|n");
 
+// Packed keys (lane_log = 2): the GGM tree stops two levels early and the
+// last level's 128-bit output is FOUR independent u32 leaves (lanes), so a
+// key over n rows has depth log2(n) - 2 and costs n/2 - 2 PRF blocks, not
+// 2n - 2.  Only eval level 0 differs from a plain key: its additions are
+// lane-wise mod 2^32 and its payload is the unit vector of the target lane.
+// Index idx splits into node = idx & (2^depth - 1), walked through the
+// tree, and lane = idx >> depth, the word of the leaf (word 0 = bits 31..0).
+constexpr int kPackedLaneLog = 2;
+constexpr u64 kPackedMinDomain = 512;  // packed domains: n = 2^d, d >= 9
+
 struct DpfKey {
-  int depth = 0;          // log2(n)
-  u64 n = 0;              // table size
+  int depth = 0;          // tree depth: log2(n) - lane_log
+  int lane_log = 0;       // 0: one u32 leaf per seed; 2: four (packed)
+  u64 n = 0;              // table size = 2^(depth + lane_log)
   u128 root = 0;          // this server's root seed
   u128 cw[2][2 * kMaxDepth] = {}; // cw[sel][level*2 + bit]; level in eval order
 };
@@ -125,12 +138,15 @@ class KeyRng {
 // walk the on-path seeds from the root down, emitting one correction-word
 // pair per level.  Semantics match the reference scheme exactly (see file
 // header); asserts the per-level invariant s0 - s1 == beta_level.
+// lane_log = kPackedLaneLog generates packed keys (n >= kPackedMinDomain;
+// beta's low 32 bits are the payload of the target lane); 0 the plain keys.
 void dpf_gen(u64 alpha, u128 beta, u64 n, int prf_method, KeyRng& rng,
-             DpfKey& k0, DpfKey& k1);
+             DpfKey& k0, DpfKey& k1, int lane_log = 0);
 
 // Evaluate one index: O(depth) PRF calls.  This is the correctness anchor
 // the GPU kernels are tested against (reference: EvaluateFlat semantics,
-// dpf_base/dpf.h:362-377).
+// dpf_base/dpf.h:362-377).  For a packed key the result is the u32 share of
+// idx (word idx >> depth of its node's leaf), zero-extended.
 u128 dpf_eval_point(const DpfKey& k, u64 idx, int prf_method);
 
 // Expand the full domain into low-32-bit shares in NATURAL index order.
@@ -163,11 +179,19 @@ void key_deserialize(const std::int32_t in[kKeyInts], DpfKey& k);
 int zlog_for_depth(int depth);
 u64 leaf_perm(u64 n, int zlog, u64 idx);       // natural -> permuted row
 u64 leaf_perm_inv(u64 n, int zlog, u64 row);   // permuted row -> natural
+// Packed tables (n = 4 * 2^D rows, D the tree depth): the four lanes of a
+// node are adjacent rows,
+//     row(idx) = leaf_perm(2^D, zlog, node) * 4 + lane
+//              = j << (zlog+3) | t << 3 | b << 2 | lane,
+// so at DFS step j thread t reads 8 consecutive rows.
+u64 packed_perm(u64 n, int zlog, u64 idx);
+u64 packed_perm_inv(u64 n, int zlog, u64 row);
 
 // Multi-GPU row sharding: rank r of W (W a power of two) owns natural
 // indices with idx % W == r; the restriction of a DPF key to that residue
 // class is itself a DPF key of depth-log2(W) obtained by walking log2(W)
-// levels from the root consuming the bits of r LSB-first.
+// levels from the root consuming the bits of r LSB-first.  Packed keys are
+// not sharded (std::invalid_argument).
 void dpf_shard_subkey(const DpfKey& k, int prf_method, u64 rank, u64 world,
                       DpfKey& out);
 

@@ -77,6 +77,11 @@ constexpr int AES_MAX_UNITS = 4;
 // accumulators of a wide row; at K <= 2 a workgroup is at most 8 waves and
 // a wave may take 256.
 constexpr int AES_MAX_UNITS_WIDE = 2;
+// The same for packed keys (LANES = 4 below).  Their fused kernel keeps two
+// lane blocks of row data (64 VGPRs) and eight shares beside the cipher: in
+// the 128 VGPRs of K = 4 it spills (44 bytes of scratch per lane), at K = 3
+// a wave may take 168 and it uses 139.
+constexpr int AES_MAX_UNITS_PACKED = 3;
 // Widest table row (u32) the fused kernel serves: W <= 4 column blocks
 constexpr int MAX_FUSED_WORDS = gpudpf::kMaxFusedWords;
 
@@ -216,9 +221,23 @@ __device__ __forceinline__ void expand_pair(uint4 seed, int i,
 // row): block 0 before the leaf cipher, which hides it, and block c+1 just
 // ahead of block c's 32 MACs, so at most two blocks (64 VGPRs) of row data
 // are in flight beside the 16*W accumulators, not all 8*W loads.
+//
+// LANES = 4 (packed keys, dpf_core.h): `depth` is the tree depth D over the
+// n / 4 nodes, and only the leaf step differs.  The leaf pair's full 128-bit
+// PRF outputs give 8 shares, v0[c] / v1[c] = word c of the leaf + word c of
+// its level-0 correction word (four u32 adds, no carries).  The table is in
+// packed_perm order, row = j << (zlog+3) | t << 3 | b << 2 | c: a thread's 8
+// rows are consecutive, and LANE BLOCK c (row c of both leaves, 8 dwordx4) is
+// column block c of a leaf's 64-word "row" in the wide-row picture above.
+// So the blocks are loaded exactly as there, block 0 before the cipher and
+// block c+1 ahead of block c's MACs; what differs is that every block MACs
+// into the SAME 16 accumulators with its own pair of shares.  The expand
+// kernel stores the 8 shares in that row order as two 16-byte stores (`out`
+// must be 16-byte aligned).  W = 1, no bins.  `n` stays the row count of the
+// table, 4 << depth.
 __device__ __forceinline__ const int* bin_ids(const int* ids) { return ids; }
 
-template <int PRF, bool FUSED, int K, int W, class... Bins>
+template <int PRF, bool FUSED, int K, int W, int LANES, class... Bins>
 __global__ __launch_bounds__(256 * K) void dpf_eval_kernel(
     const int* __restrict__ keys, const u32* __restrict__ table,
     u32* __restrict__ out, const u32* __restrict__ aes_tabs,
@@ -229,7 +248,13 @@ __global__ __launch_bounds__(256 * K) void dpf_eval_kernel(
   static_assert(W >= 1 && 16 * W <= MAX_FUSED_WORDS && (FUSED || W == 1),
                 "rows of 16*W words, wide only when fused");
   static_assert(W == 1 || K <= AES_MAX_UNITS_WIDE, "wide rows: K <= 2");
+  static_assert(LANES == 1 || (LANES == 4 && W == 1 && !BINNED),
+                "packed: four lanes, 16-word rows, no bins");
   constexpr int ROW = 16 * W;  // u32 per table row and per out row
+  // 16-word blocks loaded per leaf and step, and the u32 between the two
+  // leaves' first blocks: the row's column blocks, or a node's four lanes
+  constexpr int RB = LANES == 4 ? LANES : W;
+  constexpr int LEAF = 16 * RB;
   extern __shared__ u32 smem[];
   const EvalGeom g(depth, zlog, W);
   const int Z = g.Z, DS = g.DS, lds_base = g.lds_base;
@@ -314,6 +339,17 @@ __global__ __launch_bounds__(256 * K) void dpf_eval_kernel(
     const u32 cwl[2][2] = {{uni(cw_lds[0].x), uni(cw_lds[1].x)},
                            {uni(cw_lds[kCwPerSel].x),
                             uni(cw_lds[kCwPerSel + 1].x)}};
+    // packed: all four words of each, 16 u32
+    uint4 cw4[2][2] = {};
+    if constexpr (LANES == 4) {
+#pragma unroll
+      for (int s = 0; s < 2; ++s)
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+          const uint4 v = cw_lds[s * kCwPerSel + b];
+          cw4[s][b] = make_uint4(uni(v.x), uni(v.y), uni(v.z), uni(v.w));
+        }
+    }
 
     // The unit's bin block.  key_id is the same for the whole unit, hence
     // for the wave (Z % 64 == 0), which the compiler cannot see for K > 1.
@@ -335,28 +371,63 @@ __global__ __launch_bounds__(256 * K) void dpf_eval_kernel(
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           rq[cb & 1][0][q] = rows[4 * cb + q];
-          rq[cb & 1][1][q] = rows[4 * (W + cb) + q];
+          rq[cb & 1][1][q] = rows[4 * (RB + cb) + q];
         }
       };
       if constexpr (FUSED) {
         rows = reinterpret_cast<const uint4*>(
-            table + ((j << (zlog + 1)) + ((long long)t << 1)) * ROW);
+            table + ((j << (zlog + 1)) + ((long long)t << 1)) * LEAF);
         load_block(0);
       }
 
-      u32 v0, v1;
-      {
+      // The leaf pair's shares: v0 / v1, or at LANES = 4 word c of them in
+      // v0l[c] / v1l[c]
+      u32 v0, v1, v0l[LANES], v1l[LANES];
+      if constexpr (LANES == 1) {
         u32 p0, p1;
         prf_pair_low<PRF>(cur, T, p0, p1);
         const int sel = (int)(cur.x & 1u);
         v0 = p0 + cwl[sel][0];
         v1 = p1 + cwl[sel][1];
+      } else {
+        uint4 p0, p1;
+        const bool sel = (cur.x & 1u) != 0;
+        prf_pair<PRF>(cur, T, p0, p1);
+        const uint4 c0 = sel ? cw4[1][0] : cw4[0][0];
+        const uint4 c1 = sel ? cw4[1][1] : cw4[0][1];
+        v0l[0] = p0.x + c0.x; v0l[1] = p0.y + c0.y;
+        v0l[2] = p0.z + c0.z; v0l[3] = p0.w + c0.w;
+        v1l[0] = p1.x + c1.x; v1l[1] = p1.y + c1.y;
+        v1l[2] = p1.z + c1.z; v1l[3] = p1.w + c1.w;
       }
 
       if constexpr (FUSED) {
 #pragma unroll
-        for (int cb = 0; cb < W; ++cb) {
-          u32* acc_c = acc + 16 * cb;
+        for (int cb = 0; cb < RB; ++cb) {
+          // a column block has its own sums; the lane blocks share theirs
+          u32* acc_c = acc + (LANES == 1 ? 16 * cb : 0);
+          if constexpr (LANES == 4) {
+            v0 = v0l[cb];
+            v1 = v1l[cb];
+            if (cb + 1 < RB) {
+              // As for wide rows below: lane block cb+1 is in flight during
+              // block cb's MACs and no sooner (all 32 loads ahead of the
+              // cipher are 128 VGPRs of row data).
+              int tt = t;
+              if (cb == 0)
+                asm volatile("" : "+v"(tt)
+                             : "v"(v0l[0]), "v"(v0l[1]), "v"(v0l[2]),
+                               "v"(v0l[3]), "v"(v1l[0]), "v"(v1l[1]),
+                               "v"(v1l[2]), "v"(v1l[3]));
+              else
+                asm volatile("" : "+v"(tt)
+                             : "v"(acc[3]), "v"(acc[7]), "v"(acc[11]),
+                               "v"(acc[15]));
+              rows = reinterpret_cast<const uint4*>(
+                  table + ((j << (zlog + 1)) + ((long long)tt << 1)) * LEAF);
+              load_block(cb + 1);
+            }
+          }
           if constexpr (W > 1) if (cb + 1 < W) {
             // Block cb+1 is in flight during block cb's MACs and no sooner.
             // Left alone the compiler issues all 8*W loads ahead of the
@@ -400,9 +471,15 @@ __global__ __launch_bounds__(256 * K) void dpf_eval_kernel(
         }
       } else {
         u32* orow = out + (u64)key_id * (u64)n +
-                    (u64)((j << (zlog + 1)) + ((long long)t << 1));
-        orow[0] = v0;
-        orow[1] = v1;
+                    (u64)((j << (zlog + 1)) + ((long long)t << 1)) * LANES;
+        if constexpr (LANES == 1) {
+          orow[0] = v0;
+          orow[1] = v1;
+        } else {
+          uint4* o4 = reinterpret_cast<uint4*>(orow);
+          o4[0] = make_uint4(v0l[0], v0l[1], v0l[2], v0l[3]);
+          o4[1] = make_uint4(v1l[0], v1l[1], v1l[2], v1l[3]);
+        }
       }
 
       if (j + 1 == j_hi) break;
@@ -494,15 +571,22 @@ int slog_for(int batch, int DS) {
 // The round costs are measured for 16-word rows only.  Rows wider than that
 // allow K <= AES_MAX_UNITS_WIDE; nobody has measured their rounds, so they
 // take the largest K allowed, and a forced K is clamped to it.
-int eval_units_per_wg(int prf, int n_units, int entry_words) {
+//
+// Packed launches (lanes = 4) allow K <= AES_MAX_UNITS_PACKED, the largest K
+// whose gfx950 code has no scratch.  Their round costs are not measured
+// either: they take that K, and a forced K is clamped to it.
+int eval_units_per_wg(int prf, int n_units, int entry_words, int lanes) {
   check_entry_words(entry_words);
+  if (lanes != 1 && (lanes != 4 || entry_words != 16))
+    throw std::invalid_argument("lanes must be 1, or 4 with 16-word rows");
   if (prf != PRF_AES128) return 1;
-  const int kmax = entry_words > 16 ? AES_MAX_UNITS_WIDE : AES_MAX_UNITS;
+  const int kmax = lanes == 4 ? AES_MAX_UNITS_PACKED
+                   : entry_words > 16 ? AES_MAX_UNITS_WIDE : AES_MAX_UNITS;
   if (const char* e = std::getenv("GPUDPF_AES_UNITS")) {
     const int v = std::atoi(e);
     if (v >= 1 && v <= AES_MAX_UNITS) return v < kmax ? v : kmax;
   }
-  if (entry_words > 16) return kmax;
+  if (entry_words > 16 || lanes == 4) return kmax;
   int dev = 0, cus = 0;
   HIP_CHECK(hipGetDevice(&dev));
   HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount,
@@ -525,7 +609,7 @@ int eval_units_per_wg(int prf, int n_units, int entry_words) {
 namespace {
 
 // bins: nothing, or the binned kernel's device id array
-template <int PRF, bool FUSED, int W, class... Bins>
+template <int PRF, bool FUSED, int W, int LANES, class... Bins>
 void launch_eval_t(const int* keys, const u32* table, u32* out,
                    const u32* aes_tabs, int batch, long long n, int depth,
                    int zlog, hipStream_t stream, uint4* own_scratch,
@@ -533,17 +617,19 @@ void launch_eval_t(const int* keys, const u32* table, u32* out,
   const EvalGeom g(depth, zlog, W);
   const int slog = slog_for(batch, g.DS);
   const int n_units = batch << slog;
-  const int K = eval_units_per_wg(PRF, n_units, 16 * W);
+  const int K = eval_units_per_wg(PRF, n_units, 16 * W, LANES);
   const size_t shmem = g.lds_bytes(PRF, K);
   if (shmem > 160 * 1024)
     throw std::invalid_argument("eval launch needs more LDS than a CU has");
-  auto kern = dpf_eval_kernel<PRF, FUSED, 1, W, Bins...>;
+  auto kern = dpf_eval_kernel<PRF, FUSED, 1, W, LANES, Bins...>;
   if constexpr (PRF == PRF_AES128) {
-    if (K == 2) kern = dpf_eval_kernel<PRF, FUSED, 2, W, Bins...>;
-    if constexpr (W == 1) {
-      if (K == 3) kern = dpf_eval_kernel<PRF, FUSED, 3, W, Bins...>;
-      if (K == 4) kern = dpf_eval_kernel<PRF, FUSED, 4, W, Bins...>;
-    }
+    constexpr int KMAX = LANES == 4 ? AES_MAX_UNITS_PACKED
+                         : W > 1    ? AES_MAX_UNITS_WIDE : AES_MAX_UNITS;
+    if (K == 2) kern = dpf_eval_kernel<PRF, FUSED, 2, W, LANES, Bins...>;
+    if constexpr (KMAX >= 3)
+      if (K == 3) kern = dpf_eval_kernel<PRF, FUSED, 3, W, LANES, Bins...>;
+    if constexpr (KMAX >= 4)
+      if (K == 4) kern = dpf_eval_kernel<PRF, FUSED, 4, W, LANES, Bins...>;
   }
   allow_large_lds((const void*)kern, shmem);
   // Caller-owned scratch (launches that may overlap on different streams
@@ -581,7 +667,7 @@ void launch_eval_dispatch(std::uintptr_t keys, std::uintptr_t table,
     throw std::invalid_argument("zlog must be in [6, depth)");
   with_prf(prf, [&](auto P) {
     auto launch = [&](auto Wc) {
-      launch_eval_t<decltype(P)::value, FUSED, decltype(Wc)::value>(
+      launch_eval_t<decltype(P)::value, FUSED, decltype(Wc)::value, 1>(
           as_ptr<const int>(keys), as_ptr<const u32>(table), as_ptr<u32>(out),
           as_ptr<const u32>(aes_tabs), batch, n, depth, zlog,
           as_stream(stream), as_ptr<uint4>(scratch), scratch_bytes, bins...);
@@ -592,7 +678,50 @@ void launch_eval_dispatch(std::uintptr_t keys, std::uintptr_t table,
   });
 }
 
+// Packed launches: 16-word rows, no bins; depth is the tree depth D
+template <bool FUSED>
+void launch_packed_dispatch(std::uintptr_t keys, std::uintptr_t table,
+                            std::uintptr_t out, std::uintptr_t aes_tabs,
+                            int batch, long long n, int depth, int zlog,
+                            int prf, std::uintptr_t stream,
+                            std::uintptr_t scratch, std::size_t scratch_bytes) {
+  // a unit is 64..256 threads with at least one leaf pair each
+  if (depth < 7 || depth > gpudpf::kMaxDepth)
+    throw std::invalid_argument("packed: tree depth must be in [7, 32]");
+  if (n != (long long)4 << depth)
+    throw std::invalid_argument("packed: n must be 4 << depth");
+  if (zlog < 6 || zlog >= depth)
+    throw std::invalid_argument("zlog must be in [6, depth)");
+  if (batch <= 0) return;
+  if (out % 16 != 0)
+    throw std::invalid_argument("packed: out must be 16-byte aligned");
+  with_prf(prf, [&](auto P) {
+    launch_eval_t<decltype(P)::value, FUSED, 1, 4>(
+        as_ptr<const int>(keys), as_ptr<const u32>(table), as_ptr<u32>(out),
+        as_ptr<const u32>(aes_tabs), batch, n, depth, zlog, as_stream(stream),
+        as_ptr<uint4>(scratch), scratch_bytes);
+  });
+}
+
 }  // namespace
+
+void launch_fused_packed(std::uintptr_t keys, std::uintptr_t table,
+                         std::uintptr_t out, std::uintptr_t aes_tabs, int batch,
+                         long long n, int depth, int zlog, int prf,
+                         std::uintptr_t stream, std::uintptr_t scratch,
+                         std::size_t scratch_bytes) {
+  launch_packed_dispatch<true>(keys, table, out, aes_tabs, batch, n, depth,
+                               zlog, prf, stream, scratch, scratch_bytes);
+}
+
+void launch_expand_packed(std::uintptr_t keys, std::uintptr_t out,
+                          std::uintptr_t aes_tabs, int batch, long long n,
+                          int depth, int zlog, int prf, std::uintptr_t stream,
+                          std::uintptr_t scratch, std::size_t scratch_bytes) {
+  launch_packed_dispatch<false>(keys, /*table=*/0, out, aes_tabs, batch, n,
+                                depth, zlog, prf, stream, scratch,
+                                scratch_bytes);
+}
 
 void launch_fused(std::uintptr_t keys, std::uintptr_t table, std::uintptr_t out,
                   std::uintptr_t aes_tabs, int batch, long long n, int depth,

@@ -48,9 +48,29 @@ void launch_fused_binned(std::uintptr_t keys, std::uintptr_t table,
 // (j-split); pure host arithmetic, no HIP call.  eval_units_per_wg: the
 // (key, segment) units packed into one workgroup (1 unless prf is AES128);
 // honours GPUDPF_AES_UNITS and otherwise queries the current device.  Rows
-// wider than 16 words (entry_words as for launch_fused) take at most 2.
+// wider than 16 words (entry_words as for launch_fused) take at most 2;
+// lanes = 4 asks for a packed launch (below).
 int eval_slog(int batch, int depth, int zlog);
-int eval_units_per_wg(int prf, int n_units, int entry_words = 16);
+int eval_units_per_wg(int prf, int n_units, int entry_words = 16,
+                      int lanes = 1);
+
+// Packed keys (four u32 leaves per seed; dpf_core.h): launch_fused and
+// launch_expand for a table of n = 4 << depth rows of 16 words in
+// packed_perm(n, zlog) order, where depth is the keys' TREE depth D.
+// Checked before any HIP call: depth >= 7, n == 4 << depth, zlog in
+// [6, depth).  `out` must be 16-byte aligned.  eval_slog and
+// eval_scratch_bytes serve them as they are, called with D;
+// eval_units_per_wg with lanes = 4.
+void launch_fused_packed(std::uintptr_t keys, std::uintptr_t table,
+                         std::uintptr_t out, std::uintptr_t aes_tabs, int batch,
+                         long long n, int depth, int zlog, int prf,
+                         std::uintptr_t stream, std::uintptr_t scratch = 0,
+                         std::size_t scratch_bytes = 0);
+void launch_expand_packed(std::uintptr_t keys, std::uintptr_t out,
+                          std::uintptr_t aes_tabs, int batch, long long n,
+                          int depth, int zlog, int prf, std::uintptr_t stream,
+                          std::uintptr_t scratch = 0,
+                          std::size_t scratch_bytes = 0);
 
 // Full expansion to low-32 one-hot shares, permuted row order
 //   out: device ptr, u32 [batch][n]  (row r = leaf_perm(idx))

@@ -77,7 +77,20 @@ PYBIND11_MODULE(_hip, m) {
   m.def("eval_slog", &gpudpf_hip::eval_slog, py::arg("batch"),
         py::arg("depth"), py::arg("zlog"));
   m.def("eval_units_per_wg", &gpudpf_hip::eval_units_per_wg, py::arg("prf"),
-        py::arg("n_units"), py::arg("entry_words") = 16);
+        py::arg("n_units"), py::arg("entry_words") = 16,
+        py::arg("lanes") = 1);
+  m.def("eval_fused_packed", &gpudpf_hip::launch_fused_packed,
+        py::arg("keys"), py::arg("table"), py::arg("out"), py::arg("aes_tabs"),
+        py::arg("batch"), py::arg("n"), py::arg("depth"), py::arg("zlog"),
+        py::arg("prf"), py::arg("stream"), py::arg("scratch") = 0,
+        py::arg("scratch_bytes") = 0,
+        py::call_guard<py::gil_scoped_release>());
+  m.def("eval_expand_packed", &gpudpf_hip::launch_expand_packed,
+        py::arg("keys"), py::arg("out"), py::arg("aes_tabs"), py::arg("batch"),
+        py::arg("n"), py::arg("depth"), py::arg("zlog"), py::arg("prf"),
+        py::arg("stream"), py::arg("scratch") = 0,
+        py::arg("scratch_bytes") = 0,
+        py::call_guard<py::gil_scoped_release>());
   m.def("eval_expand", &gpudpf_hip::launch_expand, py::arg("keys"),
         py::arg("out"), py::arg("aes_tabs"), py::arg("batch"), py::arg("n"),
         py::arg("depth"), py::arg("zlog"), py::arg("prf"), py::arg("stream"),

@@ -66,6 +66,9 @@ class DPF(object):
 
     DEFAULT_PRF = _core.PRF_AES128
     KEY_INTS = _core.KEY_INTS       # 524 int32 = 2096 bytes per key
+    # log2 of the u32 leaves a key's last tree level yields per seed (int 1
+    # of a key): 0 here, 2 in PackedDPF (gpudpf/packed.py)
+    LANE_LOG = 0
 
     _PRF_NAMES = {
         _core.PRF_DUMMY: "DUMMY",
@@ -121,7 +124,8 @@ class DPF(object):
                 "number of entries in the table" % (k, n)
             )
         seed = os.urandom(128)
-        k1, k2 = _core.gen(k, self._domain(n), seed, self.prf_method)
+        k1, k2 = _core.gen(k, self._domain(n), seed, self.prf_method,
+                           packed=self.LANE_LOG != 0)
         return [torch.from_numpy(k1), torch.from_numpy(k2)]
 
     def gen_batch(self, indices, n):
@@ -133,7 +137,7 @@ class DPF(object):
         seed = os.urandom(128)
         k1s, k2s = _core.gen_batch(
             np.asarray(indices, dtype=np.int64), self._domain(n), seed,
-            self.prf_method)
+            self.prf_method, packed=self.LANE_LOG != 0)
         return torch.from_numpy(k1s), torch.from_numpy(k2s)
 
     @staticmethod
@@ -172,7 +176,7 @@ class DPF(object):
         ep = -(-e // self.ENTRY_SIZE) * self.ENTRY_SIZE
         self._n_domain = nd
         self._entry_padded = ep
-        self._depth = nd.bit_length() - 1
+        self._depth = nd.bit_length() - 1 - self.LANE_LOG  # tree depth
         self._zlog = _core.zlog_for_depth(self._depth)
         if self.device is None:
             self.device = "cuda:0" if torch.cuda.is_available() else "cpu"
@@ -191,6 +195,11 @@ class DPF(object):
             _core.leaf_perm_rows(indices.to(torch.int64).cpu().numpy(),
                                  self._n_domain, self._zlog))
 
+    def _perm_table(self):
+        """The whole natural -> row map of the set-up domain (CPU int64)."""
+        return torch.from_numpy(
+            _core.leaf_perm_table(self._n_domain, self._zlog))
+
     def _rows(self, indices):
         """Natural indices -> permuted table rows, as a device tensor."""
         dev = self._table_gpu.device
@@ -205,8 +214,7 @@ class DPF(object):
         self._table_gpu = torch.zeros((nd, self._entry_padded),
                                       dtype=torch.int32, device=dev)
         if nd <= self.PERM_MATERIALIZE_MAX:
-            self._perm_gpu = torch.from_numpy(
-                _core.leaf_perm_table(nd, self._zlog)).to(dev)
+            self._perm_gpu = self._perm_table().to(dev)
         else:
             self._perm_gpu = None
         if self.prf_method == self.PRF_AES128:
@@ -272,15 +280,24 @@ class DPF(object):
 
     def _keys_tensor(self, keys):
         kt = as_key_batch(keys)
-        # n is a u64 in u128 slot 130 (ints 520/521); depth is int 0.
+        # n is a u64 in u128 slot 130 (ints 520/521); depth is int 0, the
+        # lane log int 1.
         n = (int(kt[0, 521].item()) << 32) | (int(kt[0, 520].item()) & 0xFFFFFFFF)
         depth = int(kt[0, 0].item())
         # A batch mixing key domains would silently evaluate every key at
         # the first key's depth and produce garbage shares: reject it.
-        hdr = kt[:, [0, 520, 521]]
+        hdr = kt[:, [0, 1, 520, 521]]
         if not bool((hdr == hdr[0]).all().item()):
             raise Exception("all keys in a batch must share one domain "
-                            "(mixed depth/n header words)")
+                            "(mixed depth/lanes/n header words)")
+        # So would a packed key on a plain engine, or a plain key on a
+        # packed one, where the domains agree but the tree depths do not.
+        if int(kt[0, 1].item()) != self.LANE_LOG:
+            raise Exception(
+                "%s evaluates %s keys (lane log %d in header int 1, got %d)"
+                % (type(self).__name__,
+                   "packed" if self.LANE_LOG else "plain", self.LANE_LOG,
+                   int(kt[0, 1].item())))
         return kt, n, depth
 
     # ------------------------------------------------------------------
