@@ -13,14 +13,19 @@ serving step (key H2D, kernel(s), share D2H) in three set-ups:
   mono    one DPF over the unbinned num_bins * bin_n rows behind
           PipelinedServer, same number of keys (each costs num_bins times
           the PRFs)
+  packed  with --packed: a PackedBinnedDPF behind PipelinedServer over the
+          same tables and slot plan, packed keys for the same rows (a
+          quarter of the PRF blocks per key); needs --logn >= 9
 
 Per set-up: warm-up steps, then `--windows` timed windows of at least
 `--window-s` seconds each, all ending in a synchronise; the median window
 is reported with the minimum and maximum.  `--entry-words` (16, 32, 48 or
 64; default 16) is the row width of every table: wider than 16 words all
 three set-ups run the wide fused kernel (fused_words).  The binned and loop shares are
-compared once, exactly.  One dict line per (config, set-up), then one per
-config with the ratios; benchmarks/scrape.py reads them.
+compared once, exactly; packed shares differ from plain ones, so the packed
+set-up is checked once by reconstructing the table rows from both servers'
+packed shares, exactly.  One dict line per (config, set-up), then one per
+config with the ratios (binned_over_packed with --packed); benchmarks/scrape.py reads them.
 """
 
 import os
@@ -34,7 +39,7 @@ import time
 
 import torch
 
-from gpudpf import BinnedDPF, DPF
+from gpudpf import BinnedDPF, DPF, PackedBinnedDPF
 from gpudpf.serving import PipelinedServer
 
 
@@ -88,12 +93,17 @@ def main():
                     default=["AES128", "CHACHA20", "SALSA20"])
     ap.add_argument("--entry-words", type=int, default=16,
                     choices=list(DPF.FUSED_WIDTHS))
+    ap.add_argument("--packed", action="store_true",
+                    help="also time a PackedBinnedDPF (needs --logn >= 9)")
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--windows", type=int, default=3)
     ap.add_argument("--window-s", type=float, default=0.4)
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("binned_benchmark needs a GPU")
+    if a.packed and min(a.logn) < 9:
+        raise SystemExit("--packed needs --logn >= 9 (packed domains start "
+                         "at 512 rows)")
     dev = torch.device("cuda:0")
 
     for num_bins in a.bins:
@@ -113,13 +123,19 @@ def main():
                     loop.append(d)
                 mono = DPF(prf=prf, fused_words=a.entry_words)
                 mono.eval_init(mono_table)
+                packed = None
+                if a.packed:
+                    packed = PackedBinnedDPF(prf=prf,
+                                             fused_words=a.entry_words)
+                    packed.eval_init(tables)
                 for requests in a.requests:
                     run(a, dev, prf_name, num_bins, n, requests, binned,
-                        loop, mono)
-                del binned, loop, mono
+                        loop, mono, packed)
+                del binned, loop, mono, packed
 
 
-def run(a, dev, prf_name, num_bins, n, requests, binned, loop, mono):
+def run(a, dev, prf_name, num_bins, n, requests, binned, loop, mono,
+        packed=None):
     batch = num_bins * requests
     # `requests` consecutive slots per bin, so the per-bin loop takes slices
     plan = [b for b in range(num_bins) for _ in range(requests)]
@@ -163,6 +179,20 @@ def run(a, dev, prf_name, num_bins, n, requests, binned, loop, mono):
     res["mono"] = timed(step, drain, a.warmup, a.windows, a.window_s)
     del srv
 
+    if packed is not None:
+        pk1, pk2 = packed.gen_batch(rows, plan)
+        packed.bind_bins(plan)
+        srv = PipelinedServer(packed, batch)
+        step, drain, last = pipelined(srv, pk1)
+        res["packed"] = timed(step, drain, a.warmup, a.windows, a.window_s)
+        other = srv.collect(srv.submit(pk2))
+        rec = (last[0].to(torch.int64) - other.to(torch.int64)) \
+            .to(torch.int32)
+        want = torch.stack([packed.tables[b][r] for b, r in zip(plan, rows)])
+        if not torch.equal(rec, want):
+            raise SystemExit("packed shares do not reconstruct the rows")
+        del srv
+
     cfg = {"prf": prf_name, "num_bins": num_bins, "bin_n": n,
            "entry_words": a.entry_words, "requests": requests, "keys": batch}
     for setup, (med, lo, hi, steps) in res.items():
@@ -170,13 +200,18 @@ def run(a, dev, prf_name, num_bins, n, requests, binned, loop, mono):
                    ms_min=round(lo, 4), ms_max=round(hi, 4),
                    steps_per_window=steps,
                    keys_per_sec=round(batch / med * 1e3, 1)), flush=True)
-    print(dict(cfg, setup="summary",
-               binned_ms=round(res["binned"][0], 4),
-               loop_ms=round(res["loop"][0], 4),
-               mono_ms=round(res["mono"][0], 4),
-               loop_over_binned=round(res["loop"][0] / res["binned"][0], 2),
-               mono_over_binned=round(res["mono"][0] / res["binned"][0], 2)),
-          flush=True)
+    summary = dict(
+        cfg, setup="summary",
+        binned_ms=round(res["binned"][0], 4),
+        loop_ms=round(res["loop"][0], 4),
+        mono_ms=round(res["mono"][0], 4),
+        loop_over_binned=round(res["loop"][0] / res["binned"][0], 2),
+        mono_over_binned=round(res["mono"][0] / res["binned"][0], 2))
+    if packed is not None:
+        summary["packed_ms"] = round(res["packed"][0], 4)
+        summary["binned_over_packed"] = round(
+            res["binned"][0] / res["packed"][0], 2)
+    print(summary, flush=True)
 
 
 if __name__ == "__main__":

@@ -80,7 +80,8 @@ constexpr int AES_MAX_UNITS_WIDE = 2;
 // The same for packed keys (LANES = 4 below).  Their fused kernel keeps two
 // lane blocks of row data (64 VGPRs) and eight shares beside the cipher: in
 // the 128 VGPRs of K = 4 it spills (44 bytes of scratch per lane), at K = 3
-// a wave may take 168 and it uses 139.
+// a wave may take 168 and it uses 139.  Packed rows wider than 16 words are
+// wide first: K <= AES_MAX_UNITS_WIDE.
 constexpr int AES_MAX_UNITS_PACKED = 3;
 // Widest table row (u32) the fused kernel serves: W <= 4 column blocks
 constexpr int MAX_FUSED_WORDS = gpudpf::kMaxFusedWords;
@@ -139,7 +140,8 @@ struct EvalGeom {
 
   // Dynamic LDS bytes of a workgroup of K units: the replicated AES table
   // in front of the unit slices.  Largest: AES, K = 4, W = 1 at 137 KiB
-  // (wide AES, K = 2, W = 4: 102 KiB), within the CU's 160 KiB.
+  // (wide AES, K = 2, W = 4, packed or not: 102 KiB; packed K = 3: 119 KiB),
+  // within the CU's 160 KiB.
   std::size_t lds_bytes(int prf, int K) const {
     return ((std::size_t)aes_lds_u32(prf) + (std::size_t)K * unit_u32) * 4;
   }
@@ -233,8 +235,20 @@ __device__ __forceinline__ void expand_pair(uint4 seed, int i,
 // block c+1 ahead of block c's MACs; what differs is that every block MACs
 // into the SAME 16 accumulators with its own pair of shares.  The expand
 // kernel stores the 8 shares in that row order as two 16-byte stores (`out`
-// must be 16-byte aligned).  W = 1, no bins.  `n` stays the row count of the
-// table, 4 << depth.
+// must be 16-byte aligned); it is W = 1 and unbinned.  `n` stays the row
+// count of the table, 4 << depth.
+//
+// LANES = 4 with bins (FUSED only; the packed binned launcher) also takes
+// W = 1..4.  A bin block is n = 4 << depth rows of ROW = 16*W words in
+// packed_perm order, based at table + bin * n * ROW as above.  A thread's 8
+// rows are still consecutive, now 8*ROW words; within them leaf b, lane c,
+// column block cb, quad q is uint4 4*(b*RB + c*W + cb) + q with RB = 4*W, so
+// block k = c*W + cb is loaded by the same load_block(k), in the same double
+// buffer (block 0 before the cipher, block k+1 ahead of block k's MACs, its
+// address tied to the eight shares for k = 0 and to four sums of block k-1's
+// accumulator group after that).  Block k MACs the shares of lane k / W into
+// the 16 sums of column block k % W.  Unbinned packed kernels stay W = 1:
+// nothing reaches a wide one.
 __device__ __forceinline__ const int* bin_ids(const int* ids) { return ids; }
 
 template <int PRF, bool FUSED, int K, int W, int LANES, class... Bins>
@@ -248,12 +262,13 @@ __global__ __launch_bounds__(256 * K) void dpf_eval_kernel(
   static_assert(W >= 1 && 16 * W <= MAX_FUSED_WORDS && (FUSED || W == 1),
                 "rows of 16*W words, wide only when fused");
   static_assert(W == 1 || K <= AES_MAX_UNITS_WIDE, "wide rows: K <= 2");
-  static_assert(LANES == 1 || (LANES == 4 && W == 1 && !BINNED),
-                "packed: four lanes, 16-word rows, no bins");
+  static_assert(LANES == 1 || (LANES == 4 && (BINNED || W == 1)),
+                "packed: four lanes; bins and wide rows only together");
   constexpr int ROW = 16 * W;  // u32 per table row and per out row
   // 16-word blocks loaded per leaf and step, and the u32 between the two
-  // leaves' first blocks: the row's column blocks, or a node's four lanes
-  constexpr int RB = LANES == 4 ? LANES : W;
+  // leaves' first blocks: the row's column blocks, or those of a node's four
+  // lane rows (block k = lane * W + column block)
+  constexpr int RB = LANES == 4 ? LANES * W : W;
   constexpr int LEAF = 16 * RB;
   extern __shared__ u32 smem[];
   const EvalGeom g(depth, zlog, W);
@@ -405,10 +420,10 @@ __global__ __launch_bounds__(256 * K) void dpf_eval_kernel(
 #pragma unroll
         for (int cb = 0; cb < RB; ++cb) {
           // a column block has its own sums; the lane blocks share theirs
-          u32* acc_c = acc + (LANES == 1 ? 16 * cb : 0);
+          u32* acc_c = acc + 16 * (LANES == 1 ? cb : cb % W);
           if constexpr (LANES == 4) {
-            v0 = v0l[cb];
-            v1 = v1l[cb];
+            v0 = v0l[cb / W];
+            v1 = v1l[cb / W];
             if (cb + 1 < RB) {
               // As for wide rows below: lane block cb+1 is in flight during
               // block cb's MACs and no sooner (all 32 loads ahead of the
@@ -419,16 +434,18 @@ __global__ __launch_bounds__(256 * K) void dpf_eval_kernel(
                              : "v"(v0l[0]), "v"(v0l[1]), "v"(v0l[2]),
                                "v"(v0l[3]), "v"(v1l[0]), "v"(v1l[1]),
                                "v"(v1l[2]), "v"(v1l[3]));
-              else
+              else  // the sums block cb-1 has just added to
                 asm volatile("" : "+v"(tt)
-                             : "v"(acc[3]), "v"(acc[7]), "v"(acc[11]),
-                               "v"(acc[15]));
+                             : "v"(acc[16 * ((cb - 1) % W) + 3]),
+                               "v"(acc[16 * ((cb - 1) % W) + 7]),
+                               "v"(acc[16 * ((cb - 1) % W) + 11]),
+                               "v"(acc[16 * ((cb - 1) % W) + 15]));
               rows = reinterpret_cast<const uint4*>(
                   table + ((j << (zlog + 1)) + ((long long)tt << 1)) * LEAF);
               load_block(cb + 1);
             }
           }
-          if constexpr (W > 1) if (cb + 1 < W) {
+          if constexpr (LANES == 1 && W > 1) if (cb + 1 < W) {
             // Block cb+1 is in flight during block cb's MACs and no sooner.
             // Left alone the compiler issues all 8*W loads ahead of the
             // cipher (128 VGPRs of row data at W = 4, which spills the AES
@@ -461,8 +478,10 @@ __global__ __launch_bounds__(256 * K) void dpf_eval_kernel(
           // through the pair expansions.  The AES cipher needs those
           // registers for its lookups in flight (with them K = 4 spills),
           // so the sums are made to exist here.  The statement emits no
-          // instruction.
-          if constexpr (PRF == PRF_AES128) {
+          // instruction.  Wide packed rows need it for every PRF: without it
+          // each block's row data follows the sunk MACs and the stream
+          // ciphers spill (docs/KERNEL_NOTES.md, "Packed bins").
+          if constexpr (PRF == PRF_AES128 || (LANES == 4 && W > 1)) {
 #pragma unroll
             for (int q = 0; q < 4; ++q)
               asm volatile("" : "+v"(acc_c[4 * q]), "+v"(acc_c[4 * q + 1]),
@@ -575,13 +594,17 @@ int slog_for(int batch, int DS) {
 // Packed launches (lanes = 4) allow K <= AES_MAX_UNITS_PACKED, the largest K
 // whose gfx950 code has no scratch.  Their round costs are not measured
 // either: they take that K, and a forced K is clamped to it.
-int eval_units_per_wg(int prf, int n_units, int entry_words, int lanes) {
-  check_entry_words(entry_words);
-  if (lanes != 1 && (lanes != 4 || entry_words != 16))
-    throw std::invalid_argument("lanes must be 1, or 4 with 16-word rows");
+//
+// Wide packed launches (the packed binned kernel at 32..64 words) are wide
+// first: K <= AES_MAX_UNITS_WIDE, unmeasured, so that K.
+namespace {
+
+// The one statement of K, for any (entry_words, lanes) a kernel exists for;
+// the public queries below and launch_eval_t read it.
+int units_per_wg(int prf, int n_units, int entry_words, int lanes) {
   if (prf != PRF_AES128) return 1;
-  const int kmax = lanes == 4 ? AES_MAX_UNITS_PACKED
-                   : entry_words > 16 ? AES_MAX_UNITS_WIDE : AES_MAX_UNITS;
+  const int kmax = entry_words > 16 ? AES_MAX_UNITS_WIDE
+                   : lanes == 4     ? AES_MAX_UNITS_PACKED : AES_MAX_UNITS;
   if (const char* e = std::getenv("GPUDPF_AES_UNITS")) {
     const int v = std::atoi(e);
     if (v >= 1 && v <= AES_MAX_UNITS) return v < kmax ? v : kmax;
@@ -606,6 +629,23 @@ int eval_units_per_wg(int prf, int n_units, int entry_words, int lanes) {
   return best;
 }
 
+}  // namespace
+
+// Speaks for plain launches and, with lanes = 4, for 16-word packed ones
+// (launch_fused_packed, launch_expand_packed) only; the packed binned
+// launcher's widths are eval_units_per_wg_packed's.
+int eval_units_per_wg(int prf, int n_units, int entry_words, int lanes) {
+  check_entry_words(entry_words);
+  if (lanes != 1 && (lanes != 4 || entry_words != 16))
+    throw std::invalid_argument("lanes must be 1, or 4 with 16-word rows");
+  return units_per_wg(prf, n_units, entry_words, lanes);
+}
+
+int eval_units_per_wg_packed(int prf, int n_units, int entry_words) {
+  check_entry_words(entry_words);
+  return units_per_wg(prf, n_units, entry_words, /*lanes=*/4);
+}
+
 namespace {
 
 // bins: nothing, or the binned kernel's device id array
@@ -617,14 +657,14 @@ void launch_eval_t(const int* keys, const u32* table, u32* out,
   const EvalGeom g(depth, zlog, W);
   const int slog = slog_for(batch, g.DS);
   const int n_units = batch << slog;
-  const int K = eval_units_per_wg(PRF, n_units, 16 * W, LANES);
+  const int K = units_per_wg(PRF, n_units, 16 * W, LANES);
   const size_t shmem = g.lds_bytes(PRF, K);
   if (shmem > 160 * 1024)
     throw std::invalid_argument("eval launch needs more LDS than a CU has");
   auto kern = dpf_eval_kernel<PRF, FUSED, 1, W, LANES, Bins...>;
   if constexpr (PRF == PRF_AES128) {
-    constexpr int KMAX = LANES == 4 ? AES_MAX_UNITS_PACKED
-                         : W > 1    ? AES_MAX_UNITS_WIDE : AES_MAX_UNITS;
+    constexpr int KMAX = W > 1        ? AES_MAX_UNITS_WIDE
+                         : LANES == 4 ? AES_MAX_UNITS_PACKED : AES_MAX_UNITS;
     if (K == 2) kern = dpf_eval_kernel<PRF, FUSED, 2, W, LANES, Bins...>;
     if constexpr (KMAX >= 3)
       if (K == 3) kern = dpf_eval_kernel<PRF, FUSED, 3, W, LANES, Bins...>;
@@ -712,6 +752,45 @@ void launch_fused_packed(std::uintptr_t keys, std::uintptr_t table,
                          std::size_t scratch_bytes) {
   launch_packed_dispatch<true>(keys, table, out, aes_tabs, batch, n, depth,
                                zlog, prf, stream, scratch, scratch_bytes);
+}
+
+void launch_fused_packed_binned(std::uintptr_t keys, std::uintptr_t table,
+                                std::uintptr_t bins, std::uintptr_t out,
+                                std::uintptr_t aes_tabs, int batch,
+                                long long n, int depth, int zlog,
+                                long long num_bins, int prf,
+                                std::uintptr_t stream, std::uintptr_t scratch,
+                                std::size_t scratch_bytes, int entry_words) {
+  check_entry_words(entry_words);
+  if (depth < 7 || depth > gpudpf::kMaxDepth)
+    throw std::invalid_argument("packed: tree depth must be in [7, 32]");
+  if (n != (long long)4 << depth)
+    throw std::invalid_argument("packed: n must be 4 << depth");
+  if (zlog < 6 || zlog >= depth)
+    throw std::invalid_argument("zlog must be in [6, depth)");
+  if (num_bins < 1) throw std::invalid_argument("num_bins must be >= 1");
+  const std::size_t row_bytes = 4 * (std::size_t)entry_words;
+  if (num_bins > (long long)(SIZE_MAX / row_bytes) / n)
+    throw std::invalid_argument("num_bins * n * row bytes overflows");
+  if (batch > 0 && bins == 0)
+    throw std::invalid_argument("bins must be a device pointer");
+  if (out % 16 != 0)
+    throw std::invalid_argument("packed: out must be 16-byte aligned");
+  if (batch <= 0) return;
+  // here, not only in launch_eval_t: AES raises its LDS limit (a HIP call)
+  // before it gets there
+  if (scratch && scratch_bytes < eval_scratch_bytes(batch, depth, zlog))
+    throw std::invalid_argument("scratch buffer smaller than "
+                                "eval_scratch_bytes(batch, depth, zlog)");
+  with_prf(prf, [&](auto P) {
+    with_row_blocks(entry_words, [&](auto Wc) {
+      launch_eval_t<decltype(P)::value, true, decltype(Wc)::value, 4>(
+          as_ptr<const int>(keys), as_ptr<const u32>(table), as_ptr<u32>(out),
+          as_ptr<const u32>(aes_tabs), batch, n, depth, zlog,
+          as_stream(stream), as_ptr<uint4>(scratch), scratch_bytes,
+          as_ptr<const int>(bins));
+    });
+  });
 }
 
 void launch_expand_packed(std::uintptr_t keys, std::uintptr_t out,

@@ -49,7 +49,9 @@ void launch_fused_binned(std::uintptr_t keys, std::uintptr_t table,
 // (key, segment) units packed into one workgroup (1 unless prf is AES128);
 // honours GPUDPF_AES_UNITS and otherwise queries the current device.  Rows
 // wider than 16 words (entry_words as for launch_fused) take at most 2;
-// lanes = 4 asks for a packed launch (below).
+// lanes = 4 asks for a 16-word packed launch (launch_fused_packed,
+// launch_expand_packed) and refuses every other width: the packed binned
+// launch, which has them, is eval_units_per_wg_packed's (below).
 int eval_slog(int batch, int depth, int zlog);
 int eval_units_per_wg(int prf, int n_units, int entry_words = 16,
                       int lanes = 1);
@@ -71,6 +73,31 @@ void launch_expand_packed(std::uintptr_t keys, std::uintptr_t out,
                           int depth, int zlog, int prf, std::uintptr_t stream,
                           std::uintptr_t scratch = 0,
                           std::size_t scratch_bytes = 0);
+
+// Packed keys against bins (batch PIR), with rows of 16, 32, 48 or 64 words:
+// launch_fused_binned for packed keys.
+//   table: device ptr, u32 [num_bins][n][entry_words]; every block of
+//          n = 4 << depth rows is in packed_perm(n, zlog) order (depth is the
+//          keys' tree depth D)
+//   bins:  as for launch_fused_binned, unchecked ids in [0, num_bins)
+// Checked before any HIP call (std::invalid_argument): entry_words, depth in
+// [7, 32], n == 4 << depth, zlog in [6, depth), num_bins >= 1 and
+// num_bins * n * row bytes addressable, bins non-null when batch > 0, `out`
+// 16-byte aligned, a caller's scratch of at least eval_scratch_bytes(batch,
+// depth, zlog).  The only packed launch that serves rows wider than 16
+// words: one bin is a plain packed table.  eval_units_per_wg_packed reports
+// its units per workgroup (1 unless AES128: then at most 3 at 16 words, 2
+// above; GPUDPF_AES_UNITS is clamped to that); pure host arithmetic.
+void launch_fused_packed_binned(std::uintptr_t keys, std::uintptr_t table,
+                                std::uintptr_t bins, std::uintptr_t out,
+                                std::uintptr_t aes_tabs, int batch,
+                                long long n, int depth, int zlog,
+                                long long num_bins, int prf,
+                                std::uintptr_t stream,
+                                std::uintptr_t scratch = 0,
+                                std::size_t scratch_bytes = 0,
+                                int entry_words = 16);
+int eval_units_per_wg_packed(int prf, int n_units, int entry_words);
 
 // Full expansion to low-32 one-hot shares, permuted row order
 //   out: device ptr, u32 [batch][n]  (row r = leaf_perm(idx))

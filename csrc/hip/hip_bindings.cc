@@ -85,6 +85,15 @@ PYBIND11_MODULE(_hip, m) {
         py::arg("prf"), py::arg("stream"), py::arg("scratch") = 0,
         py::arg("scratch_bytes") = 0,
         py::call_guard<py::gil_scoped_release>());
+  m.def("eval_fused_packed_binned", &gpudpf_hip::launch_fused_packed_binned,
+        py::arg("keys"), py::arg("table"), py::arg("bins"), py::arg("out"),
+        py::arg("aes_tabs"), py::arg("batch"), py::arg("n"), py::arg("depth"),
+        py::arg("zlog"), py::arg("num_bins"), py::arg("prf"),
+        py::arg("stream"), py::arg("scratch") = 0,
+        py::arg("scratch_bytes") = 0, py::arg("entry_words") = 16,
+        py::call_guard<py::gil_scoped_release>());
+  m.def("eval_units_per_wg_packed", &gpudpf_hip::eval_units_per_wg_packed,
+        py::arg("prf"), py::arg("n_units"), py::arg("entry_words"));
   m.def("eval_expand_packed", &gpudpf_hip::launch_expand_packed,
         py::arg("keys"), py::arg("out"), py::arg("aes_tabs"), py::arg("batch"),
         py::arg("n"), py::arg("depth"), py::arg("zlog"), py::arg("prf"),

@@ -18,7 +18,7 @@ Public API parity (reference dpf.py:35-137):
 try:
     from gpudpf.dpf import DPF  # noqa: F401
     from gpudpf.binned import BinnedDPF  # noqa: F401
-    from gpudpf.packed import PackedDPF  # noqa: F401
+    from gpudpf.packed import PackedBinnedDPF, PackedDPF  # noqa: F401
     from gpudpf.dist import ReplicatedDPF, ShardedDPF  # noqa: F401
     from gpudpf.serving import GraphedServer  # noqa: F401
 except (ImportError, AttributeError):
@@ -29,5 +29,6 @@ except (ImportError, AttributeError):
     DPF = None  # type: ignore[assignment]
     BinnedDPF = None  # type: ignore[assignment]
     PackedDPF = None  # type: ignore[assignment]
+    PackedBinnedDPF = None  # type: ignore[assignment]
 
 __version__ = "0.1.0"

@@ -22,6 +22,9 @@ as they serve a DPF:
 Bin rows wider than 16 words (a collocated plan's group_size * e) need
 BinnedDPF(fused_words=32, 48 or 64): the fused kernel then walks rows of
 that many words, still one launch and one leaf expansion per key.
+
+gpudpf.PackedBinnedDPF (gpudpf/packed.py) is this class served with packed
+keys, a quarter of the PRF blocks per key, at the same widths.
 """
 
 import os
@@ -158,8 +161,7 @@ class BinnedDPF(DPF):
         self.tables = tables
         self.set_bin_sizes([t.shape[0] for t in tables])
         dev = self._setup_domain(max(self.bin_sizes), e)
-        self._perm = torch.from_numpy(
-            _core.leaf_perm_table(self._n_domain, self._zlog))
+        self._perm = self._perm_table()
         self._plan = None
         if dev.type != "cuda":
             self.eval_free()

@@ -21,34 +21,44 @@ DPF serves with one table PackedDPF serves the same way:
 including eval_init_empty / table_write / table_read, one_hot_only,
 eval_gpu_into, eval_cpu and the Graphed / Pipelined / TwoStage servers.
 
-Not built, and refused: packed keys with bins (BinnedDPF), fused rows wider
-than 16 words (they take the two-stage path), sharding (ShardedDPF), the
-"bfs" and "coop" strategies, and the HTTP server.
+PackedBinnedDPF is BinnedDPF with packed keys: batch-PIR bins of rows of 16,
+32, 48 or 64 words, one fused launch, behind the same servers and pir.serve:
+
+    d = PackedBinnedDPF(prf=DPF.PRF_AES128, fused_words=64)
+    d.eval_init(tables)                  # list of [n_b, e] int32, e <= 64
+    k1s, k2s = d.gen_batch(rows, bins)   # packed keys of the bin domain
+    d.bind_bins(bins)
+    shares = GraphedServer(d, batch=len(bins)).eval(k1s)
+
+With one bin it serves a plain table, which is the way to packed fused rows
+wider than 16 words.
+
+Not built, and refused: sharding (ShardedDPF), the HTTP server, the "bfs" and
+"coop" strategies, and PackedDPF itself with fused rows wider than 16 words
+(they take the two-stage path, or a one-bin PackedBinnedDPF).  BinnedDPF
+still refuses packed keys and PackedBinnedDPF plain ones.
 """
 
 import torch
 
 from gpudpf import _core
-from gpudpf.dpf import DPF, _hip
+from gpudpf.binned import BinnedDPF
+from gpudpf.dpf import DPF, _check_arg, _hip
 
 
-class PackedDPF(DPF):
+class _PackedLayout(object):
+    """What makes an engine a packed one, in front of DPF in the bases of
+    PackedDPF and PackedBinnedDPF: keys with lane log 2 (gen, gen_batch and
+    _keys_tensor read LANE_LOG, _setup_domain takes it off the depth),
+    domains from 512, rows in packed_perm order."""
     LANE_LOG = _core.PACKED_LANE_LOG        # 2: four lanes
     MIN_DOMAIN = _core.PACKED_MIN_DOMAIN    # 512: tree depth >= 7
-
-    def __init__(self, prf=None, device=None, fused_words=16):
-        if fused_words != self.ENTRY_SIZE:
-            raise Exception(
-                "the packed fused kernel serves rows of at most %d words "
-                "(got fused_words=%r); wider tables take the two-stage path"
-                % (self.ENTRY_SIZE, fused_words))
-        super().__init__(prf=prf, device=device, fused_words=fused_words)
 
     @staticmethod
     def _domain(n):
         """Next power of two >= 512: the tree over the n / 4 nodes keeps
         the depth >= 7 the kernels need."""
-        d = PackedDPF.MIN_DOMAIN
+        d = _PackedLayout.MIN_DOMAIN
         while d < n:
             d <<= 1
         return d
@@ -64,6 +74,17 @@ class PackedDPF(DPF):
     def _perm_table(self):
         return torch.from_numpy(
             _core.packed_perm_table(self._n_domain, self._zlog))
+
+
+class PackedDPF(_PackedLayout, DPF):
+    def __init__(self, prf=None, device=None, fused_words=16):
+        if fused_words != self.ENTRY_SIZE:
+            raise Exception(
+                "the packed fused kernel serves rows of at most %d words "
+                "(got fused_words=%r); wider tables take the two-stage path, "
+                "or a one-bin PackedBinnedDPF(fused_words=%r)"
+                % (self.ENTRY_SIZE, fused_words, fused_words))
+        super().__init__(prf=prf, device=device, fused_words=fused_words)
 
     # ------------------------------------------------------------------
     # Launches: _depth is the tree depth D, _n_domain the 4 << D rows
@@ -104,6 +125,35 @@ class PackedDPF(DPF):
                 "strategies only (got %r)" % (strategy,))
         return super().eval_gpu(keys, one_hot_only=one_hot_only,
                                 strategy=strategy, out_device=out_device)
+
+    def __repr__(self):
+        return "Packed" + super().__repr__()
+
+
+class PackedBinnedDPF(_PackedLayout, BinnedDPF):
+    """BinnedDPF served with packed keys: batch-PIR bins, a quarter of the
+    PRF blocks per key, rows of 16, 32, 48 or 64 words (fused_words), one
+    fused launch (the LANES = 4 binned kernel, csrc/hip/dpf_eval.hip).
+
+    Everything is BinnedDPF's (set_bin_sizes, gen, gen_batch, bind_bins,
+    bin_block, eval_gpu, eval_cpu, eval_gpu_into, the servers, pir.serve, the
+    refusals of one-hot output, two-stage and ingest) except that the bin
+    domain is PackedDPF._domain(largest bin) >= 512, every block is in
+    packed_perm order, _depth is the tree depth D = log2(domain) - 2 and
+    plain keys are refused.  With one bin it serves an unbinned table, the
+    only way to packed fused rows wider than 16 words."""
+
+    def _launch_binned(self, keys_gpu, bins_gpu, out_gpu, scratch=None):
+        b = len(keys_gpu)
+        ew = self._fused_entry_words()
+        stream, sptr, sbytes = self._launch_args(
+            keys_gpu, (b, self.KEY_INTS), out_gpu, (b, ew), scratch)
+        _check_arg("bins", bins_gpu, self._table_gpu.device, torch.int32, (b,))
+        _hip.eval_fused_packed_binned(
+            keys_gpu.data_ptr(), self._table_gpu.data_ptr(),
+            bins_gpu.data_ptr(), out_gpu.data_ptr(), self._aes_ptr, b,
+            self._n_domain, self._depth, self._zlog, self.num_bins,
+            self.prf_method, stream, sptr, sbytes, ew)
 
     def __repr__(self):
         return "Packed" + super().__repr__()

@@ -19,6 +19,12 @@ width limit on both sides (at most 64):
     tables = bin_tables(opt, table, max_words=64)
     dpf = BinnedDPF(fused_words=64)
 
+gpudpf.PackedBinnedDPF takes BinnedDPF's place on both sides unchanged (same
+tables, same slot plan, same decode; its keys are packed, a quarter of the
+PRF work per key, and neither engine accepts the other's):
+
+    dpf = PackedBinnedDPF(fused_words=64)
+
 Every request issues num_bins * queries_per_bin keys in the same slot
 order whatever it asks for, so the servers learn nothing from which bins
 were needed.
@@ -75,7 +81,8 @@ def make_queries(opt, dpf, indices):
 
     Makes the greedy choice of opt.fetch (most-requested groups first, at
     most queries_per_bin per bin); idle slots get a dummy key for row 0.
-    `dpf` is a BinnedDPF that knows the bin sizes.  Returns (k1s, k2s,
+    `dpf` is a BinnedDPF or PackedBinnedDPF that knows the bin sizes (any
+    engine with gen_batch(rows, bins)); the keys are of its kind.  Returns (k1s, k2s,
     slot_meaning): slot_meaning[s] is None for an idle slot, else
     (group id, the requested entries of that group)."""
     q = opt.pir.queries_per_bin
